@@ -1,6 +1,7 @@
 """bench.py -- Gibbs-sweep throughput of the HIP sampler on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload synth2|synth1|synth2_hostile|synth2_sparse|abstracts]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one full Gibbs sweep: every site of every local document resampled once, plus the per-sweep
 exchange (RCCL all-reduce of the n_kw / n_k deltas when N > 1) and the fold of the deltas into the counts.
@@ -11,10 +12,17 @@ Default workload = BASELINE.json configs[3], the configuration the metric is quo
 the corpus (generated in 64 seeded blocks) and therefore the state after every sweep are identical for every N.
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line: its roofline block comes from the HIP events of the
+timed sweeps and the stored per-site traffic (profiles/pmc_traffic.json).  --dump-outputs DIR also writes what the last timed
+sweep left (the counts and assignments in the reference's topic order; fixed seeded samples of the large arrays, float64) as
+DIR/<name>.npy, so that two builds can be compared output for output.  Everything else -- the state digests and their check
+against the stored N = 1 ones, the CPU baselines, the extra workloads, the in-run PMC passes, the N > 1 overlap probe and
+the all-reduce timed alone -- runs only with --full.
+
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks
 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>).
 
-At N = 1 the same JSON line also carries (key "extra"):
+With --full at N = 1 the same JSON line also carries (key "extra"):
   * "synth1"          BASELINE configs[2] (100k docs x 200 sites, K = 128): the roofline case BASELINE names;
   * "dense_k256"      the same corpus shape at K = 256 (the eight-documents-per-wavefront form of the 16-bit-row kernel; K = 128
                       runs sixteen, K = 512 four);
@@ -230,6 +238,50 @@ def checksum_verdict(name, docs_total, sweeps, got):
         return None, "no stored N = 1 digest for %s with %d documents after %d sweeps" % (name, docs_total, sweeps)
     want = {"n_k": t["n_k"][sweeps - 1], "n_kw": t["n_kw"][sweeps - 1]}
     return (got == want), "N = 1 digests after %d sweeps (%s): %r" % (sweeps, t.get("source", "stored"), want)
+
+
+DUMP_SEED = 2024             # the samples of --dump-outputs: a function of the inputs only, never of the state
+DUMP_ENTRIES = 1 << 20       # entries per sampled array (8 MB of float64): 32 MB in all with the sampled sites' indices
+
+
+def _dump_sample(rng, n, k):
+    """sorted indices of a seeded sample of k of range(n) (all of them when k >= n)"""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(rng.choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(sampler, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last sweep, in the reference's layout (topics in the
+    caller's numbering), as float64 .npy files (every count is an integer below 2^53: exact).  n_zk whole; n_k_v, n_d_k and z as
+    fixed seeded samples (words drawn by the sites that hold them, documents and sites uniformly) with their indices beside them.
+    -> {file name: shape}"""
+    dev, K = sampler.device, sampler.K
+    rng = np.random.default_rng(DUMP_SEED)
+    sites = _dump_sample(rng, sampler.S, DUMP_ENTRIES)
+    docs = _dump_sample(rng, sampler.D, max(1, DUMP_ENTRIES // K))
+    # words in the order the sampled sites first name them (hot words come first), at most DUMP_ENTRIES / K of them
+    site_words = sampler.word[torch.from_numpy(sites).to(dev)].cpu().numpy().astype(np.int64)
+    _, first = np.unique(site_words, return_index=True)
+    words = np.sort(site_words[np.sort(first)][:max(1, DUMP_ENTRIES // K)])
+    tp = sampler._topic_pos
+    t_sites, t_docs, t_words = (torch.from_numpy(a).to(dev) for a in (sites, docs, words))
+    out = {
+        "n_zk": sampler.n_k[tp],
+        "n_k_v_sample": sampler.n_kw[t_words][:, tp].t(),
+        "n_k_v_sample_words": t_words,
+        "n_d_k_sample": sampler.n_dk[t_docs][:, tp],
+        "n_d_k_sample_docs": t_docs + sampler.doc_base,
+        "z_sample": sampler._pos_topic[sampler.z[t_sites].to(torch.int64)],
+        "z_sample_sites": t_sites,
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for key, t in out.items():
+        a = t.to(torch.float64).contiguous().cpu().numpy()
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+        shapes[key] = list(a.shape)
+    return shapes
 
 
 def docs_per_wavefront(sampler):
@@ -1170,9 +1222,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="synth2", choices=sorted(WORKLOADS))
     ap.add_argument("--docs", type=int, default=0, help="override the number of documents of the corpus (all GPUs)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads of the N = 1 line")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 counter passes")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (counts and assignments, seeded samples of the "
+                         "large arrays, float64) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the state digests (and their N = 1 check), the CPU baselines, the extra workloads, the in-run PMC "
+                         "passes and the N > 1 probes; a plain run times the headline workload only")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra workloads of the N = 1 line")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the in-run rocprofv3 counter passes")
     ap.add_argument("--pmc-keep", default="", help="directory to keep the raw counter CSVs of the in-run passes in")
     ap.add_argument("--pmc-inner", default="", help=argparse.SUPPRESS)
     ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"),
@@ -1191,6 +1249,8 @@ def main():
     ap.add_argument("--one-device", action="store_true",
                     help="diagnostic: every rank uses cuda:0 (functional check of the N > 1 path on a one-GPU box, with gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -1258,13 +1318,17 @@ def main():
         return
     dt, kavg = time_sweeps(sampler, args.steps, args.warmup, dist, dev)
     trace("timed sweeps done: %.3f s" % dt)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(sampler, args.dump_outputs)
+        trace("outputs written to %s" % args.dump_outputs)
     tier = sampler.status.cpu().numpy().astype(np.int64)
     total_sites = sites_local
-    sums = state_checksums(sampler)
+    sums = state_checksums(sampler) if args.full else {"n_k": None, "n_kw": None}
     checksum = sums["n_k"]
     sweeps_done = sampler.sweeps_done
     comm = sampler.comm_stats() if hasattr(sampler, "comm_stats") else None
-    if dist is not None and comm is not None and sampler.rows is not None:
+    if dist is not None and comm is not None and sampler.rows is not None and args.full:
         # the collective alone (no sweep beside it), outside the timed region: what an ideal overlap could hide
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dist.barrier()
@@ -1282,7 +1346,7 @@ def main():
     # N > 1: the same shard once more with the exchange pipelined over two document ranges (the rows of the first
     # range are all-reduced while the second is sampled) -- a probe, reported next to the timed line
     probe = None
-    if dist is not None and name != "abstracts" and args.overlap < 0 and not args.no_extras:
+    if dist is not None and name != "abstracts" and args.overlap < 0 and args.full and not args.no_extras:
         keep = (info["K"], info["V"], info["N"], info["live_topics"], info["docs_local"], info["docs_total"], info["desc"])
         del sampler, info
         torch.cuda.empty_cache()
@@ -1302,8 +1366,8 @@ def main():
         live = info["live_topics"]
         ms = dt / args.steps * 1e3
         value = total_sites * args.steps / dt / 1e6
-        do_pmc = not args.no_pmc and name in PMC_WORKLOADS
-        extras_on = world == 1 and not args.no_extras and name == "synth2" and not args.docs
+        do_pmc = args.full and not args.no_pmc and name in PMC_WORKLOADS
+        extras_on = args.full and world == 1 and not args.no_extras and name == "synth2" and not args.docs
         pmc_names = [w for w in PMC_WORKLOADS if w == name or extras_on] if do_pmc else []
         line = {
             "metric": "million tokens resampled/sec (Gibbs sweep)",
@@ -1326,11 +1390,13 @@ def main():
                        "draw": "tiered: fp32 decision with a proven margin, fp64 / exact fp64 pipeline otherwise; "
                                "the result is the exact fp64 pipeline's",
                        "state_checksum_n_k": checksum, "state_checksum_n_kw": sums["n_kw"],
-                       "sweeps_behind_checksum": sweeps_done},
+                       "sweeps_behind_checksum": sweeps_done if checksum is not None else None},
             "draw_tiers": {"sites": int(sites_local) * (args.steps + args.warmup),
                            "fp32_tier_unsure": int(tier[1]), "exact_tier": int(tier[2])},
         }
-        if world > 1:
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
+        if world > 1 and args.full:
             # the state after s sweeps is identical for every N: compare with the stored single-GPU digests
             line["checksum_matches_n1"], line["checksum_note"] = checksum_verdict(name, line["config"]["docs_total"],
                                                                                   sweeps_done, sums)
@@ -1342,7 +1408,7 @@ def main():
         extra = {}
         measured = {name: dict(kernel_ms=kavg, sites=sites_local, docs=info["docs_local"], live=live,
                                shared=sampler._counts.numel() * 4)}
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             # (N > 1: rank 0 times the port on the first documents of ITS shard while the other ranks wait at the final barrier)
             line["cpu_baseline"], line["speedup_vs_cpu_port"] = cpu_baseline_json(sampler, info, name, value)
         del sampler, info
@@ -1402,7 +1468,7 @@ def main():
             extra["pipeline_abstracts"] = pipeline_extra(with_cpu=not args.no_cpu)
             extra["cascade_test"] = cascade_test_extra(with_cpu=not args.no_cpu)
         # ---- roofline: HBM-side counters collected in this run (separate rocprofv3 passes) ----
-        pmc, source = ({}, "not collected (--no-pmc)")
+        pmc, source = ({}, "not collected (--no-pmc)" if args.full else "not collected (collected with --full)")
         if pmc_names and world == 1:
             pmc, source = pmc_collect(pmc_names, keep_dir=args.pmc_keep or None, docs=args.docs)
         elif pmc_names:

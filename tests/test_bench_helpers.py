@@ -224,3 +224,48 @@ def test_the_line_sheds_its_extras_rather_than_outgrow_the_limit(bench):
 def test_host_cpu_reads_proc_cpuinfo(bench):
     model, logical, phys = bench.host_cpu()
     assert isinstance(model, str) and model and 1 <= phys <= logical
+
+
+class _StandIn(object):
+    """the fields of a GibbsSampler that bench.dump_outputs reads, as CPU tensors: K = 8 topics kept at a permuted position each"""
+
+    def __init__(self, D=300, N=40, V=500, K=8, seed=0):
+        import torch
+        g = torch.Generator().manual_seed(seed)
+        self.device, self.K, self.D, self.S, self.V, self.doc_base = torch.device("cpu"), K, D, D * N, V, 1000
+        self._pos_topic = torch.randperm(K, generator=g)
+        self._topic_pos = torch.argsort(self._pos_topic)
+        self.word = torch.randint(0, V, (self.S,), generator=g, dtype=torch.int32)
+        self.z = torch.randint(0, K, (self.S,), generator=g, dtype=torch.int32)          # device positions
+        self.n_dk = torch.randint(0, 50, (D, K), generator=g, dtype=torch.int32)
+        self.n_kw = torch.randint(0, 10 ** 6, (V, K), generator=g, dtype=torch.int32)
+        self.n_k = self.n_kw.sum(0, dtype=torch.int64).to(torch.int32)
+
+
+def test_dump_outputs_writes_the_reference_layout_and_a_fixed_sample(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays in the caller's topic numbering; the sample is the same for the same inputs whatever the state,
+    and stays within the size budget"""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_ENTRIES", 64)
+    s = _StandIn()
+    shapes = bench.dump_outputs(s, str(tmp_path / "a"))
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in shapes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    tp = s._topic_pos.numpy()
+    assert np.array_equal(got["n_zk"], s.n_k.numpy()[tp])
+    words = got["n_k_v_sample_words"].astype(np.int64)
+    assert 1 <= len(words) <= 64 // s.K and np.all(np.diff(words) > 0)
+    assert np.array_equal(got["n_k_v_sample"], s.n_kw.numpy()[words][:, tp].T)
+    docs = got["n_d_k_sample_docs"].astype(np.int64) - s.doc_base
+    assert len(docs) == 64 // s.K and np.array_equal(got["n_d_k_sample"], s.n_dk.numpy()[docs][:, tp])
+    sites = got["z_sample_sites"].astype(np.int64)
+    assert len(sites) == 64 and np.all(np.diff(sites) > 0)
+    assert np.array_equal(got["z_sample"], s._pos_topic.numpy()[s.z.numpy()[sites]])
+    # another state of the same corpus: the same indices
+    s2 = _StandIn()
+    s2.n_kw, s2.z = s2.n_kw.flip(0).contiguous(), (s2.z + 1) % s2.K
+    bench.dump_outputs(s2, str(tmp_path / "b"))
+    for k in ("n_k_v_sample_words", "n_d_k_sample_docs", "z_sample_sites"):
+        assert np.array_equal(np.load(str(tmp_path / "b" / (k + ".npy"))), got[k]), k
+    # the default budget, at most 64 MB whatever K: three samples and three index arrays of at most DUMP_ENTRIES each, n_zk
+    assert (3 * bench.DUMP_ENTRIES + 3 * bench.DUMP_ENTRIES + 8192) * 8 < 64 * 2 ** 20

@@ -9,7 +9,7 @@ OUT=gpurun_out/check
 mkdir -p $OUT
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
 timeout 2700 python -m pytest -m gpu -x -q > $OUT/gputest.log 2>&1; echo "gputest rc=$?"; grep -E "passed|failed|error" $OUT/gputest.log | tail -3
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.out 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.out 2> $OUT/bench.err; echo "bench rc=$?"
 cp gpurun_out/bench_detail.json $OUT/bench_detail.json 2>/dev/null
 tail -n 1 $OUT/bench.out > $OUT/bench_line.json
 python3 - <<'PY'

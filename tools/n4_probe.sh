@@ -6,7 +6,7 @@ RUNS=${1:-6}; shift
 OUT=gpurun_out/n4r5; mkdir -p $OUT
 for i in $(seq 1 $RUNS); do
   t0=$(date +%s.%N)
-  LLDA_BENCH_TRACE=1 LLDA_BENCH_TRACE_DUMP_S=45 timeout 150 python bench.py --gpus 4 --one-device --dist-backend gloo --steps 5 --warmup 2 --no-extras "$@" \
+  LLDA_BENCH_TRACE=1 LLDA_BENCH_TRACE_DUMP_S=45 timeout 150 python bench.py --gpus 4 --one-device --dist-backend gloo --steps 5 --warmup 2 --full --no-extras "$@" \
       > $OUT/line_$i.json 2> $OUT/err_$i.txt
   rc=$?
   t1=$(date +%s.%N); secs=$(python3 -c "print($t1 - $t0)")

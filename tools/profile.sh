@@ -13,7 +13,7 @@ REPO=$(pwd)
 P=/tmp/prof_$TAG
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT $P
-timeout 1500 python bench.py --pmc-keep $OUT/pmc > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1500 python bench.py --full --pmc-keep $OUT/pmc > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench rc=$?"; tail -c 400 $OUT/bench_default.err
 # (i) the timed line alone: the dominant kernel's average here must agree with roofline.kernel_ms of the bench line
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o default -- \
@@ -21,7 +21,7 @@ echo "bench rc=$?"; tail -c 400 $OUT/bench_default.err
 for f in $(find $P/stats -name "*_kernel_stats.csv"); do cp $f $OUT/stats_kernel_stats.csv; done
 # (ii) the same command with the extras: every other kernel of the library (the hot kernel's average then mixes workloads)
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats_x -o extras -- \
-    python $REPO/bench.py --steps 10 --warmup 2 --no-cpu --no-pmc > $P/stats_x.log 2>&1)
+    python $REPO/bench.py --steps 10 --warmup 2 --full --no-cpu --no-pmc > $P/stats_x.log 2>&1)
 for f in $(find $P/stats_x -name "*_kernel_stats.csv"); do cp $f $OUT/stats_extras_kernel_stats.csv; done
 if [ -x tools/bin/gather_ubench ]; then
   tools/bin/gather_ubench > $OUT/gather_ubench.txt 2>&1
@@ -44,11 +44,11 @@ fi
 for k in 1088 2048 3000 4296 7688; do python tools/abl_wide.py $k 2>&1 | grep "^K" >> $OUT/abl_wide.txt; done
 python tools/bench_cascade.py --test-it 150 > $OUT/bench_cascade.json 2> /dev/null
 python tools/bench_foldin.py --it 150 > $OUT/bench_foldin.json 2> /dev/null
-timeout 900 python bench.py --gpus 2 --dist-backend gloo --one-device --steps 5 --warmup 2 --no-extras > $OUT/bench_2rank_gloo_one_device.json 2> /dev/null
+timeout 900 python bench.py --gpus 2 --dist-backend gloo --one-device --steps 5 --warmup 2 --full --no-extras > $OUT/bench_2rank_gloo_one_device.json 2> /dev/null
 timeout 600 python bench.py --make-checksums 64 > $OUT/checksums_synth2.json 2> /dev/null
 # the timed line with int32 rows (the 16-bit image off): the fabric-bound form of the kernel, with its counters
 mkdir -p $OUT/int32
-LLDA_BENCH_ROWS16=off timeout 900 python bench.py --no-cpu --no-extras --pmc-keep $OUT/int32/pmc > $OUT/int32/bench.json 2> /dev/null
+LLDA_BENCH_ROWS16=off timeout 900 python bench.py --full --no-cpu --no-extras --pmc-keep $OUT/int32/pmc > $OUT/int32/bench.json 2> /dev/null
 # int32 rows against 16-bit rows on this library, states compared (tools/abl_rows16.py)
 timeout 900 python tools/abl_rows16.py synth2 k1024 synth2_hostile zipf_v20k zipf_v300k 2>&1 | grep "|" > $OUT/abl_rows16.txt
 du -sh $OUT; ls $OUT $OUT/pmc
