@@ -59,7 +59,7 @@
 #else
 #define LLDA_INFO_BUDGET_MARKS 0
 #endif
-#ifdef LLDA_QUAD_PRIO
+#if defined(LLDA_QUAD_PRIO) || defined(LLDA_QUAD_PARTS)    // (the A/B switches of the quad kernel's site loop share the bit)
 #define LLDA_INFO_QUAD_PRIO LLDA_BUILD_QUAD_PRIO
 #else
 #define LLDA_INFO_QUAD_PRIO 0

@@ -55,6 +55,22 @@ constexpr int QP_TOP = (LLDA_QUAD_PRIO) / 100 % 10, QP_DEC = (LLDA_QUAD_PRIO) / 
 constexpr int QP_TOP = 3, QP_DEC = 0, QP_BULK = 2;
 #endif
 constexpr int QNT = 128;      // threads per workgroup: two wavefronts, eight documents
+// What the site loop does not carry into the dependent phase of every iteration (each part on its own bit, for A/B builds; the
+// production build has all three: profiles/r07_quad_full_loop.md; -DLLDA_QUAD_PARTS=m overrides and sets the LLDA_QUAD_PRIO bit of
+// llda_build_info):
+//   1  FULL form of the site: while every document of the wavefront still has the sites n .. n + 3, "this document has ended" (act,
+//      more, the clamp of the look-ahead offsets) is the constant true -- the masked form runs the rest up to the longest document
+//   2  the test hooks on the margins (llda_sweep_args.debug_margin != 0) are a template parameter: production computes m directly
+//   4  z of a site is read THREE sites ahead, with the word id (which then serves as the site's word: one load less per iteration),
+//      so the old position of site n+2 is decoded in the bulk phase of iteration n from a value that landed an iteration ago --
+//      not in the dependent phase of iteration n+1 behind a wait
+#ifdef LLDA_QUAD_PARTS
+constexpr int QUAD_PARTS = (LLDA_QUAD_PARTS);
+#else
+constexpr int QUAD_PARTS = 7;
+#endif
+constexpr bool QUAD_FULL_LOOP = (QUAD_PARTS & 1) != 0, QUAD_HOOKS_OUT = (QUAD_PARTS & 2) != 0, QUAD_EARLY_DECODE = (QUAD_PARTS & 4) != 0;
+template <bool B> struct QuadForm { static constexpr bool value = B; };     // the form of a site: QuadForm<true> = FULL
 
 // The same walk for the narrower layouts of 16 slots per lane (llda_layout: T = 16): a document is LPD = 2^LB lanes x 32 slots, 64 / LPD
 // documents per wavefront --
@@ -146,10 +162,11 @@ typedef float q_v32f __attribute__((ext_vector_type(32)));
 // order rho: the pair (2a, 2a+1) holds element a of chain A and of chain B, so ONE packed instruction advances both chains.
 // Returns the wavefront's ballot of the lanes that are not sure; zn = the position every lane's document drew.
 // margin_rel, margin_data: m = total * margin_rel + margin_data * (the data-dependent form): production (0, 1), test hooks (2^-n or 2, 0)
+// HOOKS = false: m = the data-dependent form itself (what (0, 1) gives bit for bit: fl(tot * 0 + 1 * md) = md), nothing read or multiplied
 // PAD (K < KP): "no slot above lo in any lane" names position KP - 1, which holds no topic there -- the margin makes that outcome
 // impossible for a sure site (the last lane's last TOPIC has the total as its prefix), but a test hook or a later change of the margin
 // must not be able to write a topic-less position: the document is reported as not sure, and the exact tier's masked fallback decides.
-template <int LB, bool PAD = false>
+template <int LB, bool PAD = false, bool HOOKS = true>
 __device__ __forceinline__ uint64_t quad_draw(const q_v32f &xv, const q_v2f (&pa)[16], float u, float margin_rel, float margin_data, float beta,
                                               int lq, int &zn)
 {
@@ -200,7 +217,8 @@ __device__ __forceinline__ uint64_t quad_draw(const q_v32f &xv, const q_v2f (&pa
     const float t = u * tot;
     const float tg = t - prev;
     const float md = __builtin_fmaf(QM_L, X0, __builtin_fmaf(QM_T, t, __builtin_fmaf(QM_P, prev, QM_TOT * tot)));
-    const float margin = __builtin_fmaf(tot, margin_rel, margin_data * md);
+    float margin = md;
+    if constexpr (HOOKS) margin = __builtin_fmaf(tot, margin_rel, margin_data * md);
     const float lo0 = tg - margin, hi0 = tg + margin;
     // chain A or chain B?
     LLDA_MARK("search");
@@ -296,7 +314,7 @@ __device__ __forceinline__ uint64_t quad_tier1(const q_v32f &xv, const int (*s_n
     return unsure;
 }
 
-struct QuadSite { int v, f, zo, c, zn, lo, so, w; };  // (lo, so) = quad lane and slot rho of zo; w = flag of the word's row (0: wide)
+struct QuadSite { int v, f, zo, c, zn, lo, so; uint8_t w; };  // (lo, so) = quad lane and slot rho of zo; w = flag of the word's row (0: wide)
 
 // -DQUAD_PROFILE (tools/quad_phase_profile.py; never in a production build: llda_build_info reports it): wavefront 0 of workgroup 0
 // stamps the shader clock at the phase boundaries of every site and adds the differences up in status[8 + phase]
@@ -313,7 +331,8 @@ struct QuadSite { int v, f, zo, c, zn, lo, so, w; };  // (lo, so) = quad lane an
 
 // REC: {word, freq, csc_pos} of a site come as one 16-byte record (llda_sweep_args.site_rec; always for LB < 4)
 // PAD: K < KP -- positions without a topic (the K == KP instantiations stay what they were: the validity word is a constant there)
-template <int LB, bool REC = (LB < 4), bool PAD = false>
+// HOOKS: the margins of both tiers come from the kernel arguments (every debug_margin != 0); production has them compiled in
+template <int LB, bool REC = (LB < 4), bool PAD = false, bool HOOKS = false>
 __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P)
 {
     typedef QuadGeo<LB> Geo;
@@ -325,7 +344,11 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
     __shared__ int s_ndk[QT / 4][QNT][4];      // n_dk | sweep-start n_dk << 16
     __shared__ float s_pa[QT / 4][QNT][4];     // tier-0 factor fl32((n_dk + alpha) / (n_k + V*beta))
     __shared__ float s_u[QNT / LPD][2 * LPD];  // the fp32 uniforms of the next 2 LPD sites of every document
-    __shared__ int s_hot[QT][16];              // row rho: -1 (or -65536: the upper half) in the packed register that holds slot rho, else 0
+    // row rho: -1 (or -65536: the upper half) in the packed register that holds slot rho, else 0 (read as v4i)
+    __shared__ __attribute__((aligned(16))) int s_hot[QT][16];
+    // four workgroups per CU (two wavefronts per SIMD) is what the kernel is tuned for: 160 KB of LDS / 4
+    static_assert(LB != 4 || sizeof(s_nk) + sizeof(s_nk0) + sizeof(s_ndk) + sizeof(s_pa) + sizeof(s_u) + sizeof(s_hot) <= 40960,
+                  "K = 512: the static LDS of a workgroup must leave room for four workgroups on a CU");
 
     const int tid = threadIdx.x;
     for (int i = tid; i < KP; i += QNT) {
@@ -371,15 +394,21 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
             len = 0;
             s0 = site_base;
         }
-        int maxlen;
+        int maxlen, minlen;          // (minlen = 0 with a lane group without a document: its wavefront runs the masked form only)
         if constexpr (LB == 4) {
-            maxlen = max(max(__builtin_amdgcn_readlane(len, 0), __builtin_amdgcn_readlane(len, 16)),
-                         max(__builtin_amdgcn_readlane(len, 32), __builtin_amdgcn_readlane(len, 48)));
+            const int l0 = __builtin_amdgcn_readlane(len, 0), l1 = __builtin_amdgcn_readlane(len, 16);
+            const int l2 = __builtin_amdgcn_readlane(len, 32), l3 = __builtin_amdgcn_readlane(len, 48);
+            maxlen = max(max(l0, l1), max(l2, l3));
+            minlen = min(min(l0, l1), min(l2, l3));
         } else {
-            int ml = len;
+            int ml = len, nl = len;
 #pragma unroll
-            for (int m = LPD; m < 64; m <<= 1) ml = max(ml, __shfl_xor(ml, m, 64));
+            for (int m = LPD; m < 64; m <<= 1) {
+                ml = max(ml, __shfl_xor(ml, m, 64));
+                nl = min(nl, __shfl_xor(nl, m, 64));
+            }
             maxlen = __builtin_amdgcn_readfirstlane(ml);
+            minlen = __builtin_amdgcn_readfirstlane(nl);
         }
         if (maxlen == 0) continue;                                   // (uniform)
 
@@ -412,6 +441,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         const uint32_t sb = (uint32_t)(s0 - site_base) * 4u;
         const int last = len > 0 ? len - 1 : 0;
         auto off_of = [&](int n) { return opaque_u32(sb + (uint32_t)min(n, last) * 4u); };
+        auto off_full = [&](int n) { return opaque_u32(sb + (uint32_t)n * 4u); };      // FULL form: site n exists in every document
         auto load_scalars = [&](QuadSite &R, const uint32_t o) {
             R.v = gload_i32(word_b, o); R.f = gload_i32(freq_b, o); R.c = gload_i32(csc_b, o); R.zo = gload_i32(z_b, o);
         };
@@ -431,7 +461,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         // the 16-bit row of word v: chunks (e, j) = slots 8j .. 8j+7 of standard lane 2 lq + e, and the row's flag
         // (32-bit byte offsets from the image: llda_sweep checked V * 1024 < 2^32; a row is 2 KP bytes, its second half KP bytes on)
         int xp[16];
-        auto load_row16 = [&](const int v, int &flag) {
+        auto load_row16 = [&](const int v, uint8_t &flag) {
 #ifdef ABL_NOLOAD
 #pragma unroll
             for (int k = 0; k < 16; ++k) xp[k] = ((v + k) & 7) * 0x10001;      // ablation: no n_kw traffic
@@ -453,7 +483,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         // now, without prefetch (an int32 count beyond 2^24 rounds: tier 0 stays inside its margin, section 4.3; tier 1 is skipped)
         q_v32f xv;
         // (the own count has left xp already, remove_own_packed; the lanes that read an int32 row take it out here: so, own)
-        auto convert_row = [&](const int v, const int flag, const int so, const float own) {
+        auto convert_row = [&](const int v, const uint8_t flag, const int so, const float own) {
             LLDA_MARK("convert");
             const uint64_t wide_w = __ballot(flag == 0);
             if (__builtin_expect(wide_w == 0, 1)) {
@@ -509,7 +539,9 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
 
         // Software pipeline.  At the top of iteration n, xv holds the row of site n as fp32 with the site's own count taken out -- made
         // during iteration n-1, in the shadow of the LDS reads of its count update, from the row that was issued an iteration earlier
-        // still.  Scalars run two sites ahead in three rotating register sets (the loop is unrolled by three), the word ids three (wq).
+        // still.  Scalars run two sites ahead in three rotating register sets (the loop is unrolled by three), the word ids three (wq);
+        // QUAD_EARLY_DECODE: word id AND z three ahead, loaded into the set of the site that has just been decided (the set site n+3
+        // will use), so that (lo, so) of site n+2 are made in the bulk phase of iteration n from a z that landed an iteration ago.
         QuadSite R0, R1, R2;
         int wq = 0;                                      // (!REC) word of site n+2 at the top of iteration n
         if constexpr (REC) {
@@ -523,19 +555,33 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         }
         R0.zn = R1.zn = 0;
         R2.v = R2.f = R2.zo = R2.c = R2.zn = R2.lo = R2.so = R2.w = 0;
+        if constexpr (QUAD_EARLY_DECODE) {                             // word and z run three sites ahead, in the set of the site itself
+            R2.v = REC ? pv : wq;
+            R2.zo = gload_i32(z_b, off_of(2));
+        }
         load_row16(R0.v, R0.w);
         uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
         decode_old(R0);
+        if constexpr (QUAD_EARLY_DECODE) decode_old(R1);               // (every iteration decodes the site two ahead)
         if (len > 0 && lq == R0.lo) update(R0.so, R0.zo, -R0.f);      // site 0 leaves its topic (LabeledLDA.py:109-111)
         remove_own_packed(R0.so, (len > 0 && lq == R0.lo) ? R0.f : 0);
         convert_row(R0.v, R0.w, R0.so, (len > 0 && lq == R0.lo) ? (float)R0.f : 0.0f);
         load_row16(R1.v, R1.w);                                        // row of site 1
 
-        auto site = [&](const int n, QuadSite &cur, QuadSite &nxt, QuadSite &prv) {
-            const bool act = n < len, more = n + 1 < len;
+        // Two forms of one site.  The masked form is the general one: act / more = "this document has site n / n + 1".  The FULL form
+        // is the masked one with act = more = true folded in and the look-ahead offsets unclamped, NOTHING else: the driver runs it
+        // only while n + 3 < minlen (iteration n loads the scalars of site n + 2 and the word of site n + 3).
+        auto site = [&](auto form, const int n, QuadSite &cur, QuadSite &nxt, QuadSite &prv) {
+            constexpr bool FULL = decltype(form)::value;
+            const bool act = FULL || n < len, more = FULL || n + 1 < len;
+            auto off = [&](int m) { if constexpr (FULL) return off_full(m); else return off_of(m); };
             const int f = cur.f, zo = cur.zo;
             QP_START();
-            LLDA_MARK("site_top");
+            if constexpr (FULL || !QUAD_FULL_LOOP) {                   // (tools/site_loop_budget.py counts the FULL form)
+                LLDA_MARK("site_top");
+            } else {
+                LLDA_MARK("site_top_masked");
+            }
             LLDA_MARK("lds_factors");
             __builtin_amdgcn_s_setprio(QP_TOP);
             q_v2f pa[16];
@@ -558,7 +604,10 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
             const float u32 = s_u[grp][n & (2 * LPD - 1)];
             QP_MARK(0);                                                // factors + uniform issued
             int zn;
-            uint64_t unsure = quad_draw<LB, PAD>(xv, pa, u32, P.margin0_rel, P.margin0_data, beta32, lq, zn) & __ballot(act);
+            uint64_t unsure;
+            if constexpr (HOOKS) unsure = quad_draw<LB, PAD, true>(xv, pa, u32, P.margin0_rel, P.margin0_data, beta32, lq, zn);
+            else unsure = quad_draw<LB, PAD, false>(xv, pa, u32, 0.0f, 1.0f, beta32, lq, zn);
+            if constexpr (!FULL) unsure &= __ballot(act);
             QP_MARK(1);                                                // chains, scan, search, pick
             LLDA_MARK("cold_check");
             if (__builtin_expect(unsure != 0, 0)) {
@@ -573,8 +622,10 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 if (lq == 0 && ((t0_w >> gbase) & Geo::GM) && P.status) atomicAdd(P.status + 1, 1);   // statistics
                 int z1;
                 // (a document whose row was read as int32 skips tier 1: a count of 2^24 or more is not exact in xv)
-                const uint64_t still = ((P.margin_rel < 1.0 ? quad_tier1<LB, PAD>(xv, s_ndk, s_nk0, tid, lq, uniform53(ra, rb), P.alpha, P.beta, P.vbeta,
-                                                                        P.margin_rel, vm, z1) : ~0ull) | __ballot(cur.w == 0)) & __ballot(act);
+                // (HOOKS: a tier-1 margin >= 1 skips tier 1)
+                uint64_t still = ((!HOOKS || P.margin_rel < 1.0 ? quad_tier1<LB, PAD>(xv, s_ndk, s_nk0, tid, lq, uniform53(ra, rb), P.alpha, P.beta, P.vbeta,
+                                                                                  P.margin_rel, vm, z1) : ~0ull) | __ballot(cur.w == 0));
+                if constexpr (!FULL) still &= __ballot(act);
                 const bool mine0 = ((t0_w >> gbase) & Geo::GM) != 0;
                 zn = mine0 ? z1 : zn;
                 uint32_t rows = 0;
@@ -610,7 +661,12 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
             {
                 const int zpos = zn & 511, sn = zn >> 9, ln = (zn >> 3) & (LPD - 1);
                 cur.zn = zpos;
-                decode_old(nxt);
+                // the log word of the commit below, made HERE (pinned: the empty asm keeps it from sinking to its use): this site's z is
+                // dead before the scalar loads, which (QUAD_EARLY_DECODE) reuse its register for the site three ahead -- computed at the
+                // commit, the register is still live when the load is issued and the sets rotate with a move behind a vmcnt wait
+                uint32_t cword = (uint32_t)zo | ((uint32_t)zpos << 16);
+                asm volatile("" : "+v"(cword));
+                if constexpr (!QUAD_EARLY_DECODE) decode_old(nxt);     // (else: decoded an iteration ago, below)
                 const bool own_new = act && lq == ln, own_old = more && lq == nxt.lo;
                 const int sg = own_new ? sn : own_old ? nxt.so : 0;
                 const int ps = own_new ? zpos : own_old ? nxt.zo : (lq << 3);
@@ -623,13 +679,22 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 int w_next;                                            // word of site n+2 (loaded an iteration ago)
                 if constexpr (REC) {
                     prv.v = w_next = pv; prv.f = pf; prv.c = pc;       // the record of site n+2
-                    prv.zo = gload_i32(z_b, off_of(n + 2));
-                    load_rec(pv, pf, pc, off_of(n + 3));
+                    if constexpr (QUAD_EARLY_DECODE) cur.zo = gload_i32(z_b, off(n + 3));     // (prv.zo: an iteration ago)
+                    else prv.zo = gload_i32(z_b, off(n + 2));
+                    load_rec(pv, pf, pc, off(n + 3));
+                } else if constexpr (QUAD_EARLY_DECODE) {
+                    // word and z of site n+2 came an iteration ago; those of site n+3 go into THIS site's set, which is done with
+                    // them (the commit word is made above) and is the next iteration's prv: nothing to move when the sets rotate
+                    w_next = prv.v;
+                    prv.f = gload_i32(freq_b, off(n + 2)); prv.c = gload_i32(csc_b, off(n + 2));
+                    cur.v = gload_i32(word_b, off(n + 3)); cur.zo = gload_i32(z_b, off(n + 3));
                 } else {
                     w_next = wq;
-                    load_scalars(prv, off_of(n + 2));                  // scalars of site n+2 (clamped)
-                    wq = gload_i32(word_b, off_of(n + 3));
+                    load_scalars(prv, off(n + 2));                     // scalars of site n+2 (masked form: clamped)
+                    wq = gload_i32(word_b, off(n + 3));
                 }
+                // the old position of site n+2: the decode block of the next iteration only reads (lo, so)
+                if constexpr (QUAD_EARLY_DECODE) decode_old(prv);
                 QP_MARK(4);                                            // scalar / record loads of the sites ahead issued
                 // site n+1: its row (issued an iteration ago) -> fp32, own count out; then the row of site n+2 is issued
                 remove_own_packed(nxt.so, (more && lq == nxt.lo) ? nxt.f : 0);
@@ -654,8 +719,8 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                     LLDA_MARK("commit");
                     const uint32_t zoff = opaque_u32(sb + (uint32_t)n * 4u);
                     const LLDA_GLOBAL uint32_t *lp = (const LLDA_GLOBAL uint32_t *)P.commit_log + (uint32_t)(cur.c & 0x7fffffff);
-                    const uint32_t word = (uint32_t)zo | ((uint32_t)zpos << 16);
-if (lq == 0 && act) {                                // (plain stores: the compiler's vmcnt bookkeeping sees them)
+                    const uint32_t word = cword;
+                    if (lq == 0 && act) {                              // (plain stores: the compiler's vmcnt bookkeeping sees them)
                         gstore_i32(z_b, zoff, zpos);
                         *(LLDA_GLOBAL uint32_t *)lp = word;
                     }
@@ -665,12 +730,22 @@ if (lq == 0 && act) {                                // (plain stores: the compi
             LLDA_MARK("loop");
             QP_MARK(6);                                                // row prefetch, count update written, commit
         };
-        for (int n = 0;; n += 3) {                                  // (uniform trip count: the longest document of the wavefront)
-            site(n, R0, R1, R2);
+        // FULL iterations three at a time (the register sets rotate with n % 3, so the hand-over is at a multiple of three) while the
+        // last of the three still has site n + 3 in every document; the masked form from there to the longest document
+        int n = 0;
+        if constexpr (QUAD_FULL_LOOP) {
+            for (; n + 5 < minlen; n += 3) {
+                site(QuadForm<true>{}, n, R0, R1, R2);
+                site(QuadForm<true>{}, n + 1, R1, R2, R0);
+                site(QuadForm<true>{}, n + 2, R2, R0, R1);
+            }
+        }
+        for (;; n += 3) {                                           // (uniform trip count: the longest document of the wavefront)
+            site(QuadForm<false>{}, n, R0, R1, R2);
             if (n + 1 >= maxlen) break;
-            site(n + 1, R1, R2, R0);
+            site(QuadForm<false>{}, n + 1, R1, R2, R0);
             if (n + 2 >= maxlen) break;
-            site(n + 2, R2, R0, R1);
+            site(QuadForm<false>{}, n + 2, R2, R0, R1);
             if (n + 3 >= maxlen) break;
         }
 

@@ -666,15 +666,24 @@ int llda_sweep(const llda_sweep_args *a, void *stream)
         // (K = 512 with the site records measured SLOWER: 5.19 vs 4.84 ms on 125 000 documents -- four documents per wavefront are not
         // bound by the address pipeline, and the records are 4 more bytes per site)
         const dim3 qgrid((unsigned)qblocks), qblock(QNT);
+        // every debug_margin != 0 runs the instantiation that reads the margins of both tiers from the arguments (HOOKS); production has
+        // them compiled in
+        const bool hooks = a->debug_margin != 0 || !QUAD_HOOKS_OUT;
+#define LLDA_QUAD(LB_, REC_, PAD_)                                                                                                    \
+        do {                                                                                                                           \
+            if (hooks) hipLaunchKernelGGL((llda_sweep_quad_kernel<LB_, REC_, PAD_, true>), qgrid, qblock, 0, st, P);                   \
+            else hipLaunchKernelGGL((llda_sweep_quad_kernel<LB_, REC_, PAD_, false>), qgrid, qblock, 0, st, P);                        \
+        } while (0)
         if (!P.quad_pad) {
-            if (L.G == 32) hipLaunchKernelGGL((llda_sweep_quad_kernel<4>), qgrid, qblock, 0, st, P);
-            else if (L.G == 16) hipLaunchKernelGGL((llda_sweep_quad_kernel<3>), qgrid, qblock, 0, st, P);
-            else hipLaunchKernelGGL((llda_sweep_quad_kernel<2>), qgrid, qblock, 0, st, P);
+            if (L.G == 32) LLDA_QUAD(4, false, false);
+            else if (L.G == 16) LLDA_QUAD(3, true, false);
+            else LLDA_QUAD(2, true, false);
         } else {                                                          // K < KP: positions without a topic
-            if (L.G == 32) hipLaunchKernelGGL((llda_sweep_quad_kernel<4, false, true>), qgrid, qblock, 0, st, P);
-            else if (L.G == 16) hipLaunchKernelGGL((llda_sweep_quad_kernel<3, true, true>), qgrid, qblock, 0, st, P);
-            else hipLaunchKernelGGL((llda_sweep_quad_kernel<2, true, true>), qgrid, qblock, 0, st, P);
+            if (L.G == 32) LLDA_QUAD(4, false, true);
+            else if (L.G == 16) LLDA_QUAD(3, true, true);
+            else LLDA_QUAD(2, true, true);
         }
+#undef LLDA_QUAD
         const hipError_t e = hipGetLastError();
         return e == hipSuccess ? LLDA_OK : hip_fail(e);
     }
