@@ -154,7 +154,8 @@ typedef struct llda_sweep_args {
      * llda_commit_log then folds the log into the counts word by word without global atomics.  (No-return
      * global atomics saturate at ~27 G/s on MI355X, scattered 4-byte stores at ~88 G/s: tools/atomic_ubench.hip.)
      * n_kw_delta is not touched in this mode. */
-    const int32_t *csc_pos;      /* [dev] [S] index of every site in word-major (stable) order        */
+    const int32_t *csc_pos;      /* [dev] [S] index of every site in word-major (stable) order; with row16 (the
+                                    kernels of four and more documents per wavefront) every index below 2^30       */
     uint32_t      *commit_log;   /* [dev] [S] out, word-major                                         */
     int64_t  n_sites;            /* doc_off[D] - doc_off[0], the sites this call spans: must be < 2^30 (the hot
                                     kernel addresses word / freq / z / csc_pos as base + 32-bit byte offset from

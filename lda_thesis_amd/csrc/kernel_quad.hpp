@@ -56,20 +56,29 @@ constexpr int QP_TOP = 3, QP_DEC = 0, QP_BULK = 2;
 #endif
 constexpr int QNT = 128;      // threads per workgroup: two wavefronts, eight documents
 // What the site loop does not carry into the dependent phase of every iteration (each part on its own bit, for A/B builds; the
-// production build has all three: profiles/r07_quad_full_loop.md; -DLLDA_QUAD_PARTS=m overrides and sets the LLDA_QUAD_PRIO bit of
-// llda_build_info):
+// production build has 1, 2, 4 (profiles/r07_quad_full_loop.md), 16 and 32 (profiles/r08_quad_entry_key.md); -DLLDA_QUAD_PARTS=m
+// overrides and sets the LLDA_QUAD_PRIO bit of llda_build_info):
 //   1  FULL form of the site: while every document of the wavefront still has the sites n .. n + 3, "this document has ended" (act,
 //      more, the clamp of the look-ahead offsets) is the constant true -- the masked form runs the rest up to the longest document
 //   2  the test hooks on the margins (llda_sweep_args.debug_margin != 0) are a template parameter: production computes m directly
 //   4  z of a site is read THREE sites ahead, with the word id (which then serves as the site's word: one load less per iteration),
 //      so the old position of site n+2 is decoded in the bulk phase of iteration n from a value that landed an iteration ago --
 //      not in the dependent phase of iteration n+1 behind a wait
+// and the bookkeeping around the draw that turned a slot number into addresses again and again (profiles/r08_quad_entry_key.md):
+//   8  NOT in the production build (measured: nothing at K = 512 inside the combination, + 0.6 % / + 0.9 % at K = 256 / 128; the
+//      compiler already makes the address from rho in four instructions): a slot travels as its ENTRY (quad_entry below: the LDS
+//      byte offsets the slot number stands for) -- in the key of the draw, in QuadSite::so, into the count update (one AND gives the
+//      offset of the slot in s_ndk) and into the own-count removal (one AND gives the row of s_hot)
+//  16  the old position of a site is decoded by a table in LDS (s_ent[position] = the slot as it travels) instead of seven bit operations
+//  32  the "one lane owns both" branch tests its mask on the scalar unit, the log store takes the SGPR base + 32-bit offset form of the
+//      z store (positions below 2^30: llda_sweep), the own count goes into the 24-bit multiply-add without a separate sign extension
 #ifdef LLDA_QUAD_PARTS
 constexpr int QUAD_PARTS = (LLDA_QUAD_PARTS);
 #else
-constexpr int QUAD_PARTS = 7;
+constexpr int QUAD_PARTS = 55;
 #endif
 constexpr bool QUAD_FULL_LOOP = (QUAD_PARTS & 1) != 0, QUAD_HOOKS_OUT = (QUAD_PARTS & 2) != 0, QUAD_EARLY_DECODE = (QUAD_PARTS & 4) != 0;
+constexpr bool QUAD_ENTRY = (QUAD_PARTS & 8) != 0, QUAD_TABLE = (QUAD_PARTS & 16) != 0, QUAD_SMALL = (QUAD_PARTS & 32) != 0;
 template <bool B> struct QuadForm { static constexpr bool value = B; };     // the form of a site: QuadForm<true> = FULL
 
 // The same walk for the narrower layouts of 16 slots per lane (llda_layout: T = 16): a document is LPD = 2^LB lanes x 32 slots, 64 / LPD
@@ -88,13 +97,43 @@ struct QuadGeo {
     static constexpr int IS = 3 + LB;              // shift of the slot chunk i in a position
     static constexpr int DPW = 64 / LPD;           // documents per wavefront
     static constexpr uint64_t GM = LPD == 64 ? ~0ull : ((1ull << LPD) - 1);     // the lanes of a document in a ballot, shifted down
-    static constexpr uint32_t KEY_NONE = 0xFC000u | 31u << 9 | (uint32_t)(KP - 1);   // no slot above lo: the last slot of the last lane
 };
 
 // slot number of a device position: rho = 8 i + 2 c + e
 template <int LB>
 __device__ __forceinline__ int quad_rho(int pos) { return ((pos >> LB) & 0x18) | ((pos & 3) << 1) | ((pos >> 2) & 1); }
 constexpr int quad_rho_of(int i, int e, int c) { return 8 * i + 2 * c + e; }
+
+// How a slot TRAVELS (key of the draw, QuadSite::so, the argument of the count update): as the slot number rho (production) or,
+// QUAD_ENTRY, as its entry -- the byte offsets that the slot number rho stands for, each bit of rho in two places --
+//     bits 2, 3, 11 .. 13   (rho >> 2) * 2048 + (rho & 3) * 4 = byte offset of QLDS(arr, rho, 0) inside s_ndk / s_pa   (QE_NDK)
+//     bits 6 .. 10          rho << 6                          = byte offset of row rho of s_hot                        (QE_HOT)
+// so that a consumer masks where it shifted, masked and added before.  Every bit of rho maps to its own bits of the entry: the entry of
+// an OR of slot bits is the OR of their entries, which is how the search of quad_draw builds it (tests/test_quad_entry_encoding.py).
+constexpr uint32_t QE_NDK = 0x380Cu, QE_HOT = 0x7C0u;
+constexpr uint32_t quad_entry(uint32_t rho) { return ((rho >> 2) * 2048u + (rho & 3u) * 4u) | rho << 6; }
+constexpr uint32_t quad_slot(uint32_t rho) { return QUAD_ENTRY ? quad_entry(rho) : rho; }
+constexpr int QS_BITS = QUAD_ENTRY ? 14 : 5;                // width of a travelling slot
+constexpr int QK_LANE = 9 + QS_BITS;                        // key = quad lane << QK_LANE | slot << 9 | position: the minimum orders by lane first
+constexpr uint32_t QK_ZN = (1u << QK_LANE) - 1;             // slot << 9 | position
+// no slot above lo: the last slot of the last lane, under a lane field no lane has -- the largest key
+template <int LB> constexpr uint32_t QUAD_KEY_NONE = 0x3Fu << QK_LANE | quad_slot(31) << 9 | (uint32_t)(QuadGeo<LB>::KP - 1);
+constexpr bool quad_entry_ok()
+{
+    uint32_t seen_or = 0;
+    for (uint32_t r = 0; r < 32; ++r) {
+        const uint32_t en = quad_entry(r);
+        if ((en & ~(QE_NDK | QE_HOT)) || (en & QE_HOT) != r << 6 || (en & QE_NDK) != (r >> 2) * 2048u + (r & 3u) * 4u) return false;
+        for (uint32_t q = 0; q < r; ++q)
+            if (quad_entry(q) == en) return false;
+        if (quad_entry(r | 1u) != (en | quad_entry(1)) || quad_entry(r | 8u) != (en | quad_entry(8))) return false;
+        seen_or |= en;
+    }
+    return seen_or == (QE_NDK | QE_HOT);
+}
+static_assert((QE_NDK & QE_HOT) == 0, "the two fields of an entry do not overlap");
+static_assert(quad_entry_ok(), "quad_entry: injective on 0 .. 31, each field recovers its offset, OR of slots = OR of entries");
+static_assert(quad_entry(31) < (1u << 14) && (0x3Fu << QK_LANE | QK_ZN) <= 0x7FFFFFFFu, "the key fits 31 bits");
 
 // minimum of a key over the lanes of a document, in every lane: one DPP instruction per step (the compiler's form is three)
 template <int LB>
@@ -251,15 +290,15 @@ __device__ __forceinline__ uint64_t quad_draw(const q_v32f &xv, const q_v2f (&pa
     uint64_t unsure = __ballot(!(ub > hi)) | bad_total;
     // the position this lane would name, keyed by its lane; the document's first lane with a slot above lo wins (none: 511, the
     // last slot of the last lane).  Row-wide minimum: four DPP steps, one instruction each (the compiler's form is three)
-    // key = lane << 14 | slot rho << 9 | position: every search outcome sets its bit of the position AND of the slot number
+    // key = lane << QK_LANE | slot << 9 | position: every search outcome sets its bit of the position AND its bits of the travelling slot
     LLDA_MARK("pick");
     constexpr uint32_t I1 = 2u << QuadGeo<LB>::IS, I0 = 1u << QuadGeo<LB>::IS;
-    const uint32_t p = (c1 ? (I1 | 16u << 9) : 0u) | (c2 ? (I0 | 8u << 9) : 0u) | (c3 ? (2u | 4u << 9) : 0u) | (c4 ? (1u | 2u << 9) : 0u) |
-                       (c0 ? (4u | 1u << 9) : 0u) | ((uint32_t)lq << 3) | ((uint32_t)lq << 14);
-    uint32_t key = c5 ? QuadGeo<LB>::KEY_NONE : p;          // (no slot above lo: the last slot of the last lane wins only if no lane has one)
+    const uint32_t p = (c1 ? (I1 | quad_slot(16) << 9) : 0u) | (c2 ? (I0 | quad_slot(8) << 9) : 0u) | (c3 ? (2u | quad_slot(4) << 9) : 0u) |
+                       (c4 ? (1u | quad_slot(2) << 9) : 0u) | (c0 ? (4u | quad_slot(1) << 9) : 0u) | ((uint32_t)lq << 3) | ((uint32_t)lq << QK_LANE);
+    uint32_t key = c5 ? QUAD_KEY_NONE<LB> : p;              // (no slot above lo: the last slot of the last lane wins only if no lane has one)
     key = quad_min_key<LB>(key);
-    zn = (int)(key & 0x3FFFu);                              // slot << 9 | position; the lane is position >> 3 & (LPD - 1)
-    if constexpr (PAD) unsure |= __ballot(key == QuadGeo<LB>::KEY_NONE);
+    zn = (int)(key & QK_ZN);                                // slot << 9 | position; the lane is position >> 3 & (LPD - 1)
+    if constexpr (PAD) unsure |= __ballot(key == QUAD_KEY_NONE<LB>);
     return unsure;
 }
 
@@ -306,15 +345,28 @@ __device__ __forceinline__ uint64_t quad_tier1(const q_v32f &xv, const int (*s_n
     // position of chain index cnt_lo: e = k >> 4, i = (k >> 2) & 3, c = k & 3
     const uint32_t k = (uint32_t)cnt_lo;
     const uint32_t i_ = (k >> 2) & 3u, e_ = (k >> 4) & 1u, c_ = k & 3u;
-    const uint32_t p = (i_ << QuadGeo<LB>::IS) | ((uint32_t)lq << 3) | (e_ << 2) | c_ | ((8u * i_ + 2u * c_ + e_) << 9) | ((uint32_t)lq << 14);
-    uint32_t key = cnt_lo >= QT ? QuadGeo<LB>::KEY_NONE : p;
+    const uint32_t p = (i_ << QuadGeo<LB>::IS) | ((uint32_t)lq << 3) | (e_ << 2) | c_ | (quad_slot(8u * i_ + 2u * c_ + e_) << 9) | ((uint32_t)lq << QK_LANE);
+    uint32_t key = cnt_lo >= QT ? QUAD_KEY_NONE<LB> : p;
     key = quad_min_key<LB>(key);
-    zn = (int)(key & 0x3FFFu);
-    if constexpr (PAD) unsure |= __ballot(key == QuadGeo<LB>::KEY_NONE);       // (see quad_draw)
+    zn = (int)(key & QK_ZN);
+    if constexpr (PAD) unsure |= __ballot(key == QUAD_KEY_NONE<LB>);           // (see quad_draw)
     return unsure;
 }
 
-struct QuadSite { int v, f, zo, c, zn, lo, so; uint8_t w; };  // (lo, so) = quad lane and slot rho of zo; w = flag of the word's row (0: wide)
+struct QuadSite { int v, f, zo, c, zn, lo, so; uint8_t w; };  // (lo, so) = quad lane and travelling slot (quad_slot) of zo; w = flag of the word's row (0: wide)
+
+// n_dk and the factors made from it, in ONE object: the factor of a slot sits at a compile-time distance from its count, so the count
+// update addresses the slot once (ds_write_b32 ... offset:)
+struct QuadDocLds {
+    // [rho >> 2][thread][rho & 3]: a lane's four consecutive slots are 16 contiguous bytes, 16 bytes apart from lane to lane -- the 32
+    // factors of a lane come with 8 ds_read_b128 (conflict free) instead of 16 two-address reads
+    // (aligned: the 16-byte reads need the alignment that a __shared__ array of its own gets from the compiler)
+    __attribute__((aligned(16))) int ndk[QT / 4][QNT][4];      // n_dk | sweep-start n_dk << 16
+    __attribute__((aligned(16))) float pa[QT / 4][QNT][4];     // tier-0 factor fl32((n_dk + alpha) / (n_k + V*beta))
+};
+static_assert(offsetof(QuadDocLds, pa) == sizeof(int) * QT * QNT && sizeof(int) * QT * QNT < 65536 &&
+              (quad_entry(31) & QE_NDK) == (7 * QNT * 4 + 3) * sizeof(int),
+              "the factor of a slot is an immediate offset away from its count; QE_NDK is the offset of QLDS(arr, rho, 0)");
 
 // -DQUAD_PROFILE (tools/quad_phase_profile.py; never in a production build: llda_build_info reports it): wavefront 0 of workgroup 0
 // stamps the shader clock at the phase boundaries of every site and adds the differences up in status[8 + phase]
@@ -339,21 +391,23 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
     constexpr int KP = Geo::KP, LPD = Geo::LPD, G = Geo::G, IS = Geo::IS;
     __shared__ int s_nk[KP];                   // workgroup accumulator of the n_k changes
     __shared__ int s_nk0[KP];                  // the sweep-start n_k
-    // [rho >> 2][thread][rho & 3]: a lane's four consecutive slots are 16 contiguous bytes, 16 bytes apart from lane to lane -- the 32
-    // factors of a lane come with 8 ds_read_b128 (conflict free) instead of 16 two-address reads
-    __shared__ int s_ndk[QT / 4][QNT][4];      // n_dk | sweep-start n_dk << 16
-    __shared__ float s_pa[QT / 4][QNT][4];     // tier-0 factor fl32((n_dk + alpha) / (n_k + V*beta))
+    __shared__ QuadDocLds s_doc;               // n_dk | sweep-start n_dk << 16 and the tier-0 factors
+    int (*const s_ndk)[QNT][4] = s_doc.ndk;
+    float (*const s_pa)[QNT][4] = s_doc.pa;
     __shared__ float s_u[QNT / LPD][2 * LPD];  // the fp32 uniforms of the next 2 LPD sites of every document
     // row rho: -1 (or -65536: the upper half) in the packed register that holds slot rho, else 0 (read as v4i)
     __shared__ __attribute__((aligned(16))) int s_hot[QT][16];
+    // the travelling slot of every device position (QUAD_TABLE: decode_old reads it where it made it from the position's bits)
+    __shared__ uint16_t s_ent[QUAD_TABLE ? KP : 1];
     // four workgroups per CU (two wavefronts per SIMD) is what the kernel is tuned for: 160 KB of LDS / 4
-    static_assert(LB != 4 || sizeof(s_nk) + sizeof(s_nk0) + sizeof(s_ndk) + sizeof(s_pa) + sizeof(s_u) + sizeof(s_hot) <= 40960,
+    static_assert(LB != 4 || sizeof(s_nk) + sizeof(s_nk0) + sizeof(s_doc) + sizeof(s_u) + sizeof(s_hot) + (QUAD_TABLE ? sizeof(s_ent) : 0) <= 40960,
                   "K = 512: the static LDS of a workgroup must leave room for four workgroups on a CU");
 
     const int tid = threadIdx.x;
     for (int i = tid; i < KP; i += QNT) {
         s_nk[i] = 0;
         s_nk0[i] = P.n_k[i];
+        if constexpr (QUAD_TABLE) s_ent[i] = (uint16_t)quad_slot((uint32_t)quad_rho<LB>(i));
     }
     for (int i = tid; i < QT * 16; i += QNT) {
         // slot rho = 8 i + 2 c' + e sits in xp[e << 3 | (i >> 1) << 2 | (i & 1) << 1 | c' >> 1], half c' & 1 (convert_row)
@@ -374,11 +428,19 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
     typedef int v4i __attribute__((ext_vector_type(4)));
     QP_DECL;
 
+    // the count of a travelling slot in this lane's part of s_ndk; its factor sits sizeof(s_doc.ndk) bytes on (QuadDocLds)
+    char *const doc_lane = (char *)&s_doc.ndk[0][tid][0];
+    auto ndk_of = [&](int sg) -> int * {
+        if constexpr (QUAD_ENTRY) return (int *)(doc_lane + ((uint32_t)sg & QE_NDK));
+        else return &QLDS(s_doc.ndk, sg, tid);
+    };
+    auto pa_of = [&](int *nd) -> float * { return (float *)((char *)nd + offsetof(QuadDocLds, pa)); };
     auto update = [&](int sg, int pos, int df) {
-        const int w = QLDS(s_ndk, sg, tid) + df;                     // (0 <= n_dk + df < 2^16: no carry into the upper half)
-        QLDS(s_ndk, sg, tid) = w;
+        int *const c = ndk_of(sg);
+        const int w = *c + df;                                       // (0 <= n_dk + df < 2^16: no carry into the upper half)
+        *c = w;
         const int nd = w & 0xffff, nk = s_nk0[pos] + nd - (int)((uint32_t)w >> 16);
-        QLDS(s_pa, sg, tid) = tier0_factor(nd, nk, alpha32, vbeta32);
+        *pa_of(c) = tier0_factor(nd, nk, alpha32, vbeta32);
     };
 
     for (int it = 0; it < P.dpg; ++it) {
@@ -456,7 +518,11 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         };
         auto decode_old = [&](QuadSite &R) {
             R.lo = (R.zo >> 3) & (LPD - 1);
-            R.so = quad_rho<LB>(R.zo);
+            if constexpr (QUAD_TABLE) {                              // (zo is a position, as for s_nk0[zo] in the count update)
+                R.so = s_ent[R.zo];
+                asm("" : "+v"(R.so));                                // (a full register from here on: no 16-bit value to extend again at its uses)
+            }
+            else R.so = (int)quad_slot((uint32_t)quad_rho<LB>(R.zo));
         };
         // the 16-bit row of word v: chunks (e, j) = slots 8j .. 8j+7 of standard lane 2 lq + e, and the row's flag
         // (32-bit byte offsets from the image: llda_sweep checked V * 1024 < 2^32; a row is 2 KP bytes, its second half KP bytes on)
@@ -517,7 +583,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                     xv[rb_] = flag == 0 ? (float)xi[rb_] : (float)((uint32_t)xp[k] >> 16);
                 }
 #pragma unroll
-                for (int r = 0; r < QT; ++r) xv[r] -= (flag == 0 && so == r) ? own : 0.0f;
+                for (int r = 0; r < QT; ++r) xv[r] -= (flag == 0 && so == (int)quad_slot(r)) ? own : 0.0f;
             }
         };
         // The site's own count leaves the PACKED 16-bit row: the slot number so is uniform in a document, and row so of s_hot holds -1 or
@@ -528,7 +594,11 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         // paid sixteen compare-select-subtract triples.  A row that does not fit 16 bits: see convert_row.)
         auto remove_own_packed = [&](const int so, const int own) {
             LLDA_MARK("own_removal");
-            const v4i *hot = (const v4i *)&s_hot[so][0];
+            // (QUAD_SMALL: 0 <= own < 2^16, llda_sweep: max_doc_tokens -- the 24-bit multiply-add needs no sign extension in front of it)
+            if constexpr (QUAD_SMALL) __builtin_assume((uint32_t)own < 65536u);
+            const v4i *hot;
+            if constexpr (QUAD_ENTRY) hot = (const v4i *)((const char *)&s_hot[0][0] + ((uint32_t)so & QE_HOT));
+            else hot = (const v4i *)&s_hot[so][0];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const v4i h = hot[j];
@@ -647,7 +717,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                         zc = zo_r;
                         if (lane == 0 && P.status) atomicOr(P.status, 1);   // no topic with positive probability
                     }
-                    zn = (row == r) ? (zc | (quad_rho<LB>(zc) << 9)) : zn;
+                    zn = (row == r) ? (zc | (int)(quad_slot((uint32_t)quad_rho<LB>(zc)) << 9)) : zn;
                 }
             }
             QP_MARK(2);                                                // (cold tiers)
@@ -668,11 +738,17 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 asm volatile("" : "+v"(cword));
                 if constexpr (!QUAD_EARLY_DECODE) decode_old(nxt);     // (else: decoded an iteration ago, below)
                 const bool own_new = act && lq == ln, own_old = more && lq == nxt.lo;
+                // "one lane owns both" (the rare second update below).  QUAD_SMALL: the two compare masks are ANDed HERE, next to the
+                // compares, and the branch tests the scalar result -- made at the branch, behind the basic blocks of the row conversion
+                // (and through __ballot, which takes an int), the mask was rebuilt lane by lane on the vector unit
+                uint64_t both_w = 0;
+                if constexpr (QUAD_SMALL) both_w = __builtin_amdgcn_ballot_w64(own_new) & __builtin_amdgcn_ballot_w64(own_old);
                 const int sg = own_new ? sn : own_old ? nxt.so : 0;
                 const int ps = own_new ? zpos : own_old ? nxt.zo : (lq << 3);
                 const int df = own_new ? f : own_old ? -nxt.f : 0;
                 LLDA_MARK("count_update");
-                const int w0 = QLDS(s_ndk, sg, tid), k0 = s_nk0[ps];
+                int *const cg = ndk_of(sg);
+                const int w0 = *cg, k0 = s_nk0[ps];
                 QP_MARK(3);                                            // decode, the update's LDS reads issued
                 LLDA_MARK("scalars");
                 __builtin_amdgcn_s_setprio(QP_BULK);
@@ -704,10 +780,11 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 load_row16(w_next, prv.w);
                 LLDA_MARK("count_update");
                 const int w = w0 + df;                                  // (0 <= n_dk + df < 2^16: no carry into the upper half)
-                QLDS(s_ndk, sg, tid) = w;
+                *cg = w;
                 const int nd = w & 0xffff, nk = k0 + nd - (int)((uint32_t)w >> 16);
-                QLDS(s_pa, sg, tid) = tier0_factor(nd, nk, alpha32, vbeta32);
-                if (__builtin_expect(__ballot(own_new && own_old) != 0, 0)) {
+                *pa_of(cg) = tier0_factor(nd, nk, alpha32, vbeta32);
+                if constexpr (!QUAD_SMALL) both_w = __ballot(own_new && own_old);
+                if (__builtin_expect(both_w != 0, 0)) {
                     LLDA_MARK("rare_second_update");
                     if (own_new && own_old) update(nxt.so, nxt.zo, -nxt.f);
                 }
@@ -718,11 +795,20 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 {
                     LLDA_MARK("commit");
                     const uint32_t zoff = opaque_u32(sb + (uint32_t)n * 4u);
-                    const LLDA_GLOBAL uint32_t *lp = (const LLDA_GLOBAL uint32_t *)P.commit_log + (uint32_t)(cur.c & 0x7fffffff);
                     const uint32_t word = cword;
-                    if (lq == 0 && act) {                              // (plain stores: the compiler's vmcnt bookkeeping sees them)
-                        gstore_i32(z_b, zoff, zpos);
-                        *(LLDA_GLOBAL uint32_t *)lp = word;
+                    if constexpr (QUAD_SMALL) {
+                        // (the shift drops bit 31, the flag the two-document kernel keeps there; llda_sweep: positions below 2^30)
+                        const uint32_t loff = (uint32_t)cur.c << 2;
+                        if (lq == 0 && act) {                          // (plain stores: the compiler's vmcnt bookkeeping sees them)
+                            gstore_i32(z_b, zoff, zpos);
+                            gstore_i32((int32_t *)P.commit_log, loff, (int)word);
+                        }
+                    } else {
+                        const LLDA_GLOBAL uint32_t *lp = (const LLDA_GLOBAL uint32_t *)P.commit_log + (uint32_t)(cur.c & 0x7fffffff);
+                        if (lq == 0 && act) {
+                            gstore_i32(z_b, zoff, zpos);
+                            *(LLDA_GLOBAL uint32_t *)lp = word;
+                        }
                     }
                 }
 #endif

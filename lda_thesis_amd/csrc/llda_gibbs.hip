@@ -645,6 +645,9 @@ int llda_sweep(const llda_sweep_args *a, void *stream)
         if (!(a->max_doc_tokens > 0 && a->max_doc_tokens < 65536)) return LLDA_E_BAD_ARG;
         if ((reinterpret_cast<uintptr_t>(a->n_kw16) | reinterpret_cast<uintptr_t>(a->n_kw)) & 15) return LLDA_E_BAD_ARG;
         if (a->V >= (1LL << 22)) return LLDA_E_BAD_ARG;                  // (the image is addressed with 32-bit byte offsets)
+        // (the commit log too: log position << 2 in 32 bits.  The general check above refuses such a call for the site arrays' sake;
+        // this kernel's own reason stands here, with its other bounds, so that it survives a change of that one)
+        if (a->n_sites >= (1LL << 30)) return LLDA_E_BAD_ARG;
         if (L.G <= 16 && !P.site_rec) return LLDA_E_BAD_ARG;             // (8 / 16 documents per wavefront read 16-byte site records)
         if (a->n_sites < 1) return LLDA_OK;                              // (documents without sites: nothing to sample)
         P.n_kw16 = a->n_kw16;

@@ -430,7 +430,8 @@ class GibbsSampler(object):
         four_waves = 0 < tokens_max < 65536
         if auto and not four_waves and V * KP * 4 < self.ROWS16_MIN_BYTES:
             return
-        quad = bool(self._quad_wanted is not False and four_waves and _native.quad_ok(self.K) and V < (1 << 22))
+        quad = bool(self._quad_wanted is not False and four_waves and _native.quad_ok(self.K) and V < (1 << 22)
+                    and self.S < (1 << 30))      # (the quad kernel addresses the commit log with 32-bit byte offsets)
         two_doc = _native.rows16_ok(self.K)       # the kernel with static flags (bit 31 of csc_pos, site_row): K = 512, 1024
         if quad and self._quad_wanted is None:
             # sites whose word has a count beyond 16 bits somewhere in its row: rare, or the two-document kernel's prefetched int32 rows
@@ -440,7 +441,7 @@ class GibbsSampler(object):
                 quad = False
         if self._quad_wanted and not quad:
             raise ValueError("quad=True: needs a K with llda_quad_ok (16 slots per lane in 8, 16 or 32 lanes: K = 100, 128, 200, 256, 400, 512 ...), "
-                             "documents of fewer than 65 536 tokens and a vocabulary below 2^22 words")
+                             "documents of fewer than 65 536 tokens, a vocabulary below 2^22 words and fewer than 2^30 sites")
         if not quad and not (two_doc and bool(self._rows16_fits().any())):
             return
         n32 = (V + 1) * KP
