@@ -5,7 +5,8 @@
  * the same body as  SubLDA.training_iteration  (/root/reference/CascadeLDA.py:397-421).  This header
  * is the boundary a maintainer binds (ctypes stub in INTEGRATION.md) to replace those two methods,
  * the count initialisation loops (LabeledLDA.py:89-92, CascadeLDA.py:382-385) and the thinning
- * read-outs (LabeledLDA.py:231-239, :256-265).
+ * read-outs (LabeledLDA.py:231-239, :256-265).  ABI 22 adds what the reference does not have: llda_count_hist, the counts of
+ * counts from which alpha and beta (0.001 there: CascadeLDA's constants and the defaults of train_it) are estimated while training.
  *
  * Conventions
  *   - every pointer marked [dev] is a DEVICE pointer (HBM of the current HIP device); the library
@@ -39,7 +40,7 @@
 extern "C" {
 #endif
 
-#define LLDA_ABI_VERSION 21
+#define LLDA_ABI_VERSION 22
 #define LLDA_MAX_K 7688          /* every K up to here splits into <= 64 pairwise leaves                       */
 #define LLDA_MAX_KP 8192         /* longest padded row: 64 leaves x 128                                        */
 #define LLDA_MAX_LEAVES 8        /* "narrow" layouts: one lane group of <= 64 lanes x <= 16 slots per document  */
@@ -351,6 +352,22 @@ int llda_pack_image(const int32_t *n_kw, int64_t n, int32_t bits, void *img, voi
 int llda_count_init(const int64_t *doc_off, const int32_t *word, const int32_t *freq,
                     const int32_t *z, int64_t D, int32_t K,
                     int32_t *n_dk, int32_t *n_kw, int32_t *n_k, void *stream);
+
+/* Counts of counts (ABI 22): hist[n] += the number of ALLOWED entries of a (rows, KP) count matrix in device order that hold the
+ * value n.  Minka's fixed point for a symmetric Dirichlet prior depends on n_dk and n_kw only through these histograms
+ * (lda_thesis_amd/priors.py); they are exact, independent of order, and summed over ranks with an integer all-reduce.
+ * For every row r and every position p < KP whose (lane, slot) bit -- llda_layout.pos_lane / pos_slot -- is set in the row's
+ * mask, v = counts[r*KP + p]:  (uint32_t)v < n_bins: hist[v] += 1 (zeros go to hist[0]); otherwise i = (*over_n)++ and
+ * over_val[i] = v when i < over_cap (nothing is ever written past over_cap; over_n still counts every such value; the order of
+ * over_val is unspecified).  Masked-off entries are not counted whatever they hold, and the masks lane_masks() builds have no bit
+ * in the padding.  hist and over_n ACCUMULATE (the caller zeroes them), so a matrix may be passed as several row ranges.
+ *   mask_per_row 1: lab_mask is [rows*G], row r uses mask row r (n_dk with llda_sweep_args.lab_mask);
+ *   mask_per_row 0: lab_mask is [G], one mask row for every row (n_kw with the all-topics row).
+ * rows == 0 is a no-op; n_bins >= 1, over_cap >= 0 (0 with a non-NULL buffer is legal), counts 16-byte aligned.  Every layout is
+ * taken (narrow and wide); indices are 64-bit (rows * KP may exceed 2^31). */
+int llda_count_hist(const int32_t *counts, int64_t rows, int32_t K, const uint16_t *lab_mask, int32_t mask_per_row,
+                    int32_t n_bins, unsigned long long *hist, int32_t *over_val, int64_t over_cap,
+                    unsigned long long *over_n, void *stream);
 
 /* log-likelihood read-out (LabeledLDA.py:256-265): out_doc[d] (dev, double[D]) = sum over the sites
  * of document d of  -log( sum_k phi[k][w] * theta[d][k] ),  phi/theta as get_phi/get_theta

@@ -9,7 +9,9 @@ What differs from the reference:
     over all documents (per-document snapshot semantics, keyed Philox draw) instead of a python loop;
   * the sufficient statistics live in HBM; ``n_d_k``, ``n_k_v``, ``n_zk``, ``z_dn`` are properties that
     materialise them on the host in the reference's shapes and dtypes (LabeledLDA.py:73-79);
-  * ``perplexity()`` (LabeledLDA.py:256-265) and the test-time fold-in sampler run on the device.
+  * ``perplexity()`` (LabeledLDA.py:256-265) and the test-time fold-in sampler run on the device;
+  * new, off by default: ``optimize_priors()`` and ``run_training(..., optimize_interval=n)`` fit alpha and beta to the counts while
+    training (the reference fixes both); ``prior_trace`` records the fitted values.
 Text preparation uses ``lda_thesis_amd.text`` instead of gensim (not installable here).
 """
 import csv
@@ -111,6 +113,7 @@ class LabeledLDA(object):
         self._ph_hat = HostOrDevice(np.zeros((self.K, self.V), dtype=float))
         self._th_hat = HostOrDevice(np.zeros((self.D, self.K), dtype=float))
         self.cur_perplx = []
+        self.prior_trace = []                         # (sweep, alpha, beta) of every optimize_priors() inside run_training
 
         doc_off, word, freq = csr_from_doc_tups(self.doc_tups)
         self._doc_off = doc_off
@@ -212,15 +215,56 @@ class LabeledLDA(object):
         self._sampler.sweep()
         self._sampler.post_status()
 
-    def run_training(self, iters, thinning):
+    def optimize_priors(self, alpha=True, beta=True, n_bins=65536):
+        """Fit the symmetric priors to the current state: Minka's fixed point (``priors.py``) on the counts of counts of n_dk and
+        n_kw, which ``llda_count_hist`` builds on the device.  alpha / beta = False leaves that prior as it is.  Sets self.alpha /
+        self.beta and the sampler's priors (next sweep, read-outs, perplexity, fold-in, pickling) and returns the pair.
+        COLLECTIVE with several ranks; rank 0's two doubles are broadcast so that every rank hands its kernels identical scalars."""
+        from . import priors
+        sm = self._sampler
+        sm.check_status()
+        hist_dk, over_dk, hist_kw, over_kw = sm.count_histograms(n_bins)
+        est = priors.estimate(self.alpha if alpha else None, self.beta if beta else None, hist_dk=hist_dk, over_dk=over_dk,
+                              classes=self._doc_classes(), hist_kw=hist_kw, over_kw=over_kw, n_k=sm.n_zk(), V=self.V)
+        a = float(est.alpha) if alpha else float(self.alpha)
+        b = float(est.beta) if beta else float(self.beta)
+        if _world_size() > 1:
+            import torch
+            import torch.distributed as dist
+            # (a SUM in which every rank but 0 adds zeros: exact, and the collective the sweeps already use)
+            t = torch.tensor([a, b] if _rank() == 0 else [0.0, 0.0], dtype=torch.float64, device=sm.device)
+            dist.all_reduce(t)
+            a, b = float(t[0]), float(t[1])
+        sm.set_priors(a, b)
+        self.alpha, self.beta = a, b
+        return a, b
+
+    def _doc_classes(self):
+        """the unique (allowed topics, tokens) pairs of ALL documents with their multiplicities (static; every rank holds the
+        full labs and CSR on the host)"""
+        from . import priors
+        cls = self.__dict__.get("_classes")
+        if cls is None:
+            doc_off, _, freq = csr_from_doc_tups(self.doc_tups)
+            pre = np.concatenate([[0], np.cumsum(np.asarray(freq, dtype=np.int64))])
+            cls = self._classes = priors.doc_classes(self.labs.sum(axis=1), pre[doc_off[1:]] - pre[doc_off[:-1]])
+        return cls
+
+    def run_training(self, iters, thinning, optimize_interval=0, optimize_burn_in=0):
         """Sweep loop with thinning read-outs and running means: reference LabeledLDA.py:127-153.  phi, theta,
-        their running means and the three guards are evaluated on the device (llda_readout_phi / _theta)."""
+        their running means and the three guards are evaluated on the device (llda_readout_phi / _theta).
+        optimize_interval = n > 0: after the sweeps optimize_burn_in + n, + 2n, ... of this call ``optimize_priors()`` refits
+        alpha and beta (before that sweep's thinning read-out, if it has one) and (sweep, alpha, beta) is appended to
+        ``self.prior_trace``; 0 (default): the priors never change."""
         import torch
         sm = self._sampler
         lo, hi = self._bounds[_rank()], self._bounds[_rank() + 1]
         for n in range(iters):
             self.training_iteration()
             print('Running iteration # %d ' % (n + 1))
+            if optimize_interval > 0 and n + 1 > optimize_burn_in and (n + 1 - optimize_burn_in) % optimize_interval == 0:
+                a, b = self.optimize_priors()
+                self.__dict__.setdefault("prior_trace", []).append((n + 1, a, b))
             if (n + 1) % thinning != 0:
                 continue
             sm.check_status()

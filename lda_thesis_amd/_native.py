@@ -16,7 +16,7 @@ MAX_KP = 8192
 MAX_LEAVES = 8          # narrow layouts
 MAX_WIDE_LEAVES = 64
 MAX_ROUNDS = 4
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _c_i32, _c_i64, _c_u32, _c_u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
 _c_p, _c_d = ctypes.c_void_p, ctypes.c_double
@@ -72,7 +72,7 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
-           "llda_readout_phi", "llda_readout_theta", "llda_selftest_div")
+           "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist")
 
 _LIB = None
 
@@ -131,6 +131,8 @@ def lib():
     L.llda_apply_delta.argtypes = [_c_p, _c_p, _c_i64, _c_p]
     L.llda_count_init.restype = ctypes.c_int
     L.llda_count_init.argtypes = [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i32, _c_p, _c_p, _c_p, _c_p]
+    L.llda_count_hist.restype = ctypes.c_int
+    L.llda_count_hist.argtypes = [_c_p, _c_i64, _c_i32, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_i64, _c_p, _c_p]
     L.llda_loglik.restype = ctypes.c_int
     L.llda_loglik.argtypes = [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i32, _c_d, _c_d,
                               _c_p, _c_p]
@@ -303,6 +305,15 @@ def apply_delta(counts, delta):
 def count_init(doc_off, word, freq, z, D, K, n_dk, n_kw, n_k):
     _launch(n_kw, lib().llda_count_init, "llda_count_init", _ptr(doc_off), _ptr(word), _ptr(freq), _ptr(z), int(D), int(K),
             _ptr(n_dk), _ptr(n_kw), _ptr(n_k))
+
+
+def count_hist(counts, K, lab_mask, mask_per_row, hist, over_val, over_n, over_cap=None):
+    """llda_count_hist on the current torch stream: hist (int64 [n_bins]) += how many allowed entries of ``counts`` (int32 (rows, KP),
+    device order) hold every value; values outside 0 .. n_bins-1 are appended to over_val (int32 [over_cap]) and counted in over_n
+    (int64 [1]).  lab_mask: the lane masks of the rows ((rows, G), mask_per_row=True) or one mask row ((G,), False); over_cap: how
+    many values over_val may take (default: all it holds)."""
+    _launch(hist, lib().llda_count_hist, "llda_count_hist", _ptr(counts), int(counts.shape[0]), int(K), _ptr(lab_mask), 1 if mask_per_row else 0,
+            int(hist.numel()), _ptr(hist), _ptr(over_val), int(over_val.numel() if over_cap is None else over_cap), _ptr(over_n))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

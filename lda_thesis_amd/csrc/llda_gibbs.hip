@@ -31,6 +31,7 @@
 //   kernel_readout.hpp  llda_loglik_kernel, llda_readout_phi / _theta kernels (thinning read-outs)
 //   kernel_foldin.hpp   llda_foldin_kernel (test-time sampler)
 //   kernel_counts.hpp   llda_commit_log_kernel, llda_apply_delta_kernel, llda_count_init_kernel, self test
+//   kernel_hist.hpp     llda_count_hist_kernel    counts of counts of n_dk / n_kw (the estimate of alpha and beta)
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
@@ -59,6 +60,7 @@
 #include "kernel_readout.hpp"
 #include "kernel_foldin.hpp"
 #include "kernel_counts.hpp"
+#include "kernel_hist.hpp"
 #include "kernel_wide.hpp"
 
 namespace {
@@ -912,6 +914,47 @@ int llda_count_init(const int64_t *doc_off, const int32_t *word, const int32_t *
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(llda_count_init_kernel, dim3((unsigned)blocks), dim3(64 * waves), lds,
                        (hipStream_t)stream, doc_off, word, freq, z, D, L.KP, n_dk, n_kw, n_k);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+}
+
+int llda_count_hist(const int32_t *counts, int64_t rows, int32_t K, const uint16_t *lab_mask, int32_t mask_per_row, int32_t n_bins,
+                    unsigned long long *hist, int32_t *over_val, int64_t over_cap, unsigned long long *over_n, void *stream)
+{
+    if (rows < 0 || n_bins < 1 || over_cap < 0 || (mask_per_row != 0 && mask_per_row != 1)) return LLDA_E_BAD_ARG;
+    if (rows > 0 && (!counts || !lab_mask || !hist || !over_val || !over_n)) return LLDA_E_BAD_ARG;
+    int rc;
+    const llda_layout *Lp = layout_of(K, &rc);
+    if (rc) return rc;
+    const llda_layout &L = *Lp;
+    if (rows == 0) return LLDA_OK;
+    if ((reinterpret_cast<uintptr_t>(counts) & 15) || (reinterpret_cast<uintptr_t>(lab_mask) & 1) ||
+        ((reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(over_n)) & 7) || (reinterpret_cast<uintptr_t>(over_val) & 3))
+        return LLDA_E_BAD_ARG;
+    if (rows > INT64_MAX / L.KP) return LLDA_E_BAD_ARG;
+    HParams P;
+    P.counts = reinterpret_cast<const int4 *>(counts);
+    P.cpr = L.KP / 4;                                  // (KP = 8 * leaves * T: a multiple of 8)
+    P.n4 = rows * P.cpr;
+    P.mask = lab_mask;
+    P.mask_stride = mask_per_row ? L.G : 0;
+    P.G = L.G;
+    P.g_magic = (uint32_t)(((1u << 24) + (uint32_t)L.G - 1u) / (uint32_t)L.G);
+    P.n_bins = (uint32_t)n_bins;
+    P.hist = hist; P.over_val = over_val; P.over_cap = over_cap; P.over_n = over_n;
+    const int64_t tile = 256 * HIST_UNROLL;
+    int64_t blocks = (P.n4 + tile - 1) / tile;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    P.step256_r = 256 / P.cpr;
+    P.step256_c = 256 % P.cpr;
+    const int64_t skip = (blocks - 1) * tile;
+    P.tile_rows = skip / P.cpr;
+    P.tile_c = (int32_t)(skip % P.cpr);
+    const dim3 grid((unsigned)blocks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (L.T % 4 == 0) hipLaunchKernelGGL(llda_count_hist_kernel<4>, grid, block, 0, st, P);
+    else if (L.T == 2) hipLaunchKernelGGL(llda_count_hist_kernel<2>, grid, block, 0, st, P);
+    else hipLaunchKernelGGL(llda_count_hist_kernel<1>, grid, block, 0, st, P);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LLDA_OK : hip_fail(e);
 }

@@ -538,11 +538,15 @@ class GibbsSampler(object):
             self._flag_rows16()            # row totals changed: a row may no longer fit 16 bits (or fit now)
 
     # ------------------------------------------------------------------ masks
+    def _all_topics_row(self):
+        """the lane masks of a document that allows every topic (no bit in the padding), as (1, G) int64 on the device"""
+        row = self.layout.lane_masks(np.ones((1, self.K))).astype(np.int64)
+        return torch.from_numpy(row).to(self.device)
+
     def _make_masks(self, labs):
         lay, dev = self.layout, self.device
         if labs is None:
-            row = lay.lane_masks(np.ones((1, self.K)))[0].astype(np.int64)
-            m = torch.from_numpy(row).to(dev).expand(self.D, lay.G)
+            m = self._all_topics_row().expand(self.D, lay.G)
         elif isinstance(labs, tuple):
             lab_off, lab_idx = labs
             lab_off = torch.as_tensor(np.asarray(lab_off), dtype=torch.int64, device=dev)
@@ -558,9 +562,12 @@ class GibbsSampler(object):
             if labs.shape != (self.D, self.K):
                 raise ValueError("labs must be (D, K) = (%d, %d)" % (self.D, self.K))
             m = torch.from_numpy(lay.lane_masks(labs).astype(np.int64)).to(dev)
-        # stored as the uint16 bit pattern in an int16 tensor
-        m = torch.where(m >= 32768, m - 65536, m).to(torch.int16).contiguous()
-        return m
+        return self._u16(m)
+
+    @staticmethod
+    def _u16(m):
+        """lane masks (int64, 0 .. 65535) stored as the uint16 bit pattern in an int16 tensor"""
+        return torch.where(m >= 32768, m - 65536, m).to(torch.int16).contiguous()
 
     def _make_live(self):
         """per document the device positions of its allowed topics (draw order) for the sparse-label kernel.  A document that allows
@@ -889,6 +896,56 @@ class GibbsSampler(object):
         if st & 4:
             raise RuntimeError("a count left 0 .. 65535 where it is kept in 16 bits (a flagged row of n_kw, or an entry of n_dk "
                                "under the four-wave kernel): the counts handed to the sampler do not belong to its corpus")
+
+    # ------------------------------------------------------------------ priors
+    def set_priors(self, alpha, beta):
+        """new alpha / beta from the next sweep on (and in theta, phi, perplexity from now on).  Only values of the domain the
+        kernels of this sampler were selected for: alpha, beta >= 1e-6 and V*beta < 2^40 (``priors.in_domain``).  With several
+        ranks every rank must pass the same two doubles."""
+        from . import priors
+        alpha, beta = float(alpha), float(beta)
+        if not priors.in_domain(alpha, beta, self.V):
+            raise ValueError("set_priors(%r, %r): needs alpha, beta >= %g and V*beta < 2^40" % (alpha, beta, priors.PRIOR_MIN))
+        self.alpha, self.beta = alpha, beta
+
+    def count_histograms(self, n_bins=65536):
+        """counts of counts for the estimate of the priors (``priors.py``), by llda_count_hist: (hist_dk, over_dk, hist_kw, over_kw)
+        as numpy int64 arrays.  hist_dk[n] = how many ALLOWED (document, topic) entries of n_dk hold n -- over the documents of
+        every rank when the shard is one of several --, hist_kw[n] the same for the (topic, word) entries of n_kw; over_* are the
+        sorted values at or above n_bins.  At most tokens // n_bins + 1 entries can hold n_bins or more, which sizes the overflow
+        buffers; counts that break that bound (they do not belong to the corpus) raise, on every rank alike.
+        COLLECTIVE with several ranks: one int64 SUM all-reduce whose size depends only on n_bins, the number of ranks and the
+        corpus' token count."""
+        n_bins = int(n_bins)
+        if n_bins < 1:
+            raise ValueError("n_bins must be at least 1")
+        dev = self.device
+        shared = self.sharded and _dist_active(self.group)
+        world, rank = 1, 0
+        if shared:
+            import torch.distributed as dist
+            world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
+        # the tokens of ALL ranks, the same number on every rank (n_k is replicated and sweeps conserve its sum)
+        cap = int(self.n_k.sum(dtype=torch.int64).item()) // n_bins + 1
+        # [hist_dk (n_bins) | per rank: number of overflow values, then up to cap of them]: one buffer, one all-reduce
+        buf = torch.zeros((n_bins + world * (1 + cap),), dtype=torch.int64, device=dev)
+        mine = buf[n_bins + rank * (1 + cap):n_bins + (rank + 1) * (1 + cap)]
+        over = torch.zeros((cap,), dtype=torch.int32, device=dev)
+        _native.count_hist(self.n_dk, self.K, self.lab_mask, True, buf[:n_bins], over, mine[:1])
+        mine[1:] = over
+        kw = torch.zeros((n_bins + 1,), dtype=torch.int64, device=dev)
+        over_kw = torch.zeros((cap,), dtype=torch.int32, device=dev)
+        _native.count_hist(self.n_kw, self.K, self._u16(self._all_topics_row()), False, kw[:n_bins], over_kw, kw[n_bins:])
+        if shared:
+            dist.all_reduce(buf, group=self.group)
+        host, kw_host = buf.cpu().numpy(), kw.cpu().numpy()
+        slots = host[n_bins:].reshape(world, 1 + cap)
+        n_over_kw = int(kw_host[n_bins])
+        if int(slots[:, 0].max()) > cap or n_over_kw > cap:
+            raise RuntimeError("more than tokens // n_bins + 1 = %d counts are outside 0 .. %d: the counts handed to the sampler do "
+                               "not belong to its corpus" % (cap, n_bins - 1))
+        over_dk = np.sort(np.concatenate([slots[r, 1:1 + int(slots[r, 0])] for r in range(world)]))
+        return (host[:n_bins].copy(), over_dk, kw_host[:n_bins].copy(), np.sort(over_kw[:n_over_kw].cpu().numpy().astype(np.int64)))
 
     # ------------------------------------------------------------------ read-outs
     def loglik_sum(self):
