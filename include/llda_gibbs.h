@@ -227,7 +227,7 @@ int         llda_build_info(void);
 const char *llda_strerror(int code);
 int         llda_last_hip_error(void);
 /* sizeof of the argument structs as the library was compiled (0 llda_layout, 1 llda_sweep_args, 2 llda_batch_args,
- * 3 llda_foldin_args): a binding checks its own struct definitions against it once, at load time. */
+ * 3 llda_foldin_args, 4 llda_rank_args): a binding checks its own struct definitions against it once, at load time. */
 int         llda_struct_size(int which);
 /* Fill *out for K topics.  Mirrors numpy's pairwise-sum recursion (np.sum at LabeledLDA.py:117). */
 int         llda_layout_init(int32_t K, llda_layout *out);
@@ -450,6 +450,51 @@ typedef struct llda_foldin_args {
 } llda_foldin_args;
 
 int llda_foldin(const llda_foldin_args *args, void *stream);
+
+/* Rank the label scores of D documents and return the top-n labels plus the per-document ingredients of every metric the
+ * reference's harness prints: what LabeledLDA.get_pred / get_preds (/root/reference/LabeledLDA.py:214-229) and one_roc, rates,
+ * macro_auc_roc, n_error and get_f1 (/root/reference/evaluate_LabeledLDA.py:8-93) compute on the host, from ONE sort per document
+ * (DESIGN.md 4.4b).  Additive to ABI 22.
+ *   score [D][ld] doubles, row-major, in REFERENCE topic order (column = topic id), ld >= K the row stride -- not a group layout;
+ *   truth [D][K] uint8 or NULL, non-zero = the document carries the label.
+ * Only the columns first .. K-1 are ranked (the harness passes 1: 'root' is in no label set); L = K - first.  No other column of
+ * score or truth is ever read.  Scores compare as IEEE values (-0 == +0, +-inf ordinary).  Per document:
+ *   order    score descending, then topic id ascending: np.argsort(-row, kind="stable")
+ *   top_idx  [D][top_n] int32, top_val [D][top_n] double: the first top_n of the order, padded with -1 / 0.0 when L < top_n
+ *   n_thr    T, the number of distinct scores (the thresholds of one_roc, highest first: a label is predicted when its score is >=
+ *            the threshold; tp_i / fp_i = predicted labels with / without truth, P / N = ranked labels with / without truth)
+ *   auc      (double)A / (double)(2 P N),  A = sum_{i=1..T-1} (fp_i - fp_{i-1}) (tp_i + tp_{i-1}): the trapezoid of macro_auc_roc over
+ *            (fp / N, tp / P) in exact arithmetic with one rounding (the curve starts at the first threshold, as the reference's);
+ *            NaN when P = 0, N = 0 or T < 2
+ *   f1       the largest 2 tp_i / (2 tp_i + fp_i + P - tp_i) over the thresholds with tp_i > 0, chosen by integer
+ *            cross-multiplication, then one IEEE division (get_f1: its nan thresholds are those with tp = 0); NaN when there is none
+ *   hit_rank 1-based rank in the order of the best-ranked true label, 0 when there is none: n_error(n) is the share of documents
+ *            with 0 < hit_rank <= n.  (numpy's default argsort in n_error leaves the order of tied scores open; here it is the order above.)
+ *   flags    bit 1: P = 0, 2: N = 0, 4: T < 2, 8: every ranked score equals 0 (the documents evaluate_LabeledLDA.py's report drops),
+ *            16: a NaN among the ranked scores -- then flags = 16, n_thr = 0, auc = f1 = NaN, hit_rank = 0, top_idx = -1, top_val = 0.
+ * Every output pointer may be NULL on its own; with truth == NULL auc, f1 and hit_rank are not written and bits 1 and 2 never set.
+ * Every output is an integer or one correctly rounded division of two exact integers: bit-identical whatever the geometry.
+ * D == 0 is a no-op; K in 1 .. LLDA_MAX_K (LLDA_E_BAD_K otherwise), 0 <= first < K, ld >= K, 0 <= top_n <= 16. */
+typedef struct llda_rank_args {
+    const double  *score;        /* [dev] [D][ld]                                                */
+    const uint8_t *truth;        /* [dev] [D][K] or NULL                                         */
+    int64_t  D;
+    int64_t  ld;
+    int32_t  K, first, top_n, reserved;
+    int32_t *top_idx;            /* [dev] [D][top_n] or NULL                                     */
+    double  *top_val;            /* [dev] [D][top_n] or NULL                                     */
+    int32_t *n_thr;              /* [dev] [D] or NULL                                            */
+    double  *auc;                /* [dev] [D] or NULL                                            */
+    double  *f1;                 /* [dev] [D] or NULL                                            */
+    int32_t *hit_rank;           /* [dev] [D] or NULL                                            */
+    int32_t *flags;              /* [dev] [D] or NULL                                            */
+} llda_rank_args;
+#define LLDA_RANK_NO_POSITIVE 1
+#define LLDA_RANK_NO_NEGATIVE 2
+#define LLDA_RANK_ONE_THRESHOLD 4
+#define LLDA_RANK_ALL_ZERO 8
+#define LLDA_RANK_NAN 16
+int llda_rank_labels(const llda_rank_args *args, void *stream);
 
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds

@@ -333,6 +333,34 @@ class LabeledLDA(object):
     def get_preds(self, all_th, n=5):
         return [self.get_pred(all_th[d, :], n) for d in range(all_th.shape[0])]
 
+    # ---- predictions and metrics without the (D, K) download (new; the methods above are the reference's) ----
+    def _test_theta_device(self, newdocs, it, thinning, seed, stream_id):
+        from .foldin import TEST_STREAM, fold_in
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
+        return fold_in(ph, self.alpha, tups, it, thinning, self.seed if seed is None else seed,
+                       TEST_STREAM if stream_id is None else stream_id, keep_device=True)
+
+    def predict(self, newdocs, it, thinning, n=5, seed=None, stream_id=None):
+        """``get_preds(run_test(newdocs, it, thinning), n)`` with the ranking on the device (llda_rank_labels): the fold-in's loads
+        never leave it, only the n (label, load) pairs per document do.  n <= 16.  Equal loads are ordered by label index
+        ascending (``get_pred``'s argsort leaves their order open); the loads themselves are the same bits."""
+        from . import ranking
+        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        r = ranking.rank_labels(th, None, first=0, top_n=n).host()
+        names = np.array(list(self.labelmap.keys()))
+        m = min(n, self.K)
+        return [list(zip(names[idx[:m]], val[:m])) for idx, val in zip(r["top_idx"], r["top_val"])]
+
+    def score_test(self, newdocs, labels, it, thinning, seed=None, stream_id=None):
+        """Fold ``newdocs`` in and score the loads against ``labels`` (one list of label strings per document, what
+        ``evaluate.binary_yreal`` takes) by the rules of the harness's report: dict(auc, one_error, two_error, f1, kept, dropped)
+        (``ranking.metrics``).  Per document 28 bytes come back to the host."""
+        from . import ranking
+        from .evaluate import binary_yreal
+        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        return ranking.metrics(ranking.rank_labels(th, binary_yreal(labels, self.labelmap), first=1, top_n=0))
+
     # ---- pickling: pull the device state to the host (evaluate_LabeledLDA.py:142-145 pickles the model)
     def __getstate__(self):
         self.ph_hat, self.th_hat                      # bring the running means to the host

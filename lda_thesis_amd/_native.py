@@ -68,11 +68,18 @@ class LldaBatchArgs(ctypes.Structure):
                 ("beta", _c_d), ("seed", _c_u64), ("sweep", _c_u32), ("reserved", _c_u32)]
 
 
+class LldaRankArgs(ctypes.Structure):
+    """struct llda_rank_args (include/llda_gibbs.h)."""
+    _fields_ = [("score", _c_p), ("truth", _c_p), ("D", _c_i64), ("ld", _c_i64), ("K", _c_i32), ("first", _c_i32),
+                ("top_n", _c_i32), ("reserved", _c_i32), ("top_idx", _c_p), ("top_val", _c_p), ("n_thr", _c_p), ("auc", _c_p),
+                ("f1", _c_p), ("hit_rank", _c_p), ("flags", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
-           "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist")
+           "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels")
 
 _LIB = None
 
@@ -142,13 +149,15 @@ def lib():
     L.llda_readout_phi.argtypes = [_c_p, _c_p, _c_p, _c_i64, _c_i32, _c_d, _c_i32, _c_d, _c_d, _c_p, _c_p, _c_p]
     L.llda_readout_theta.restype = ctypes.c_int
     L.llda_readout_theta.argtypes = [_c_p, _c_p, _c_i64, _c_i32, _c_d, _c_i32, _c_d, _c_d, _c_p, _c_p]
+    L.llda_rank_labels.restype = ctypes.c_int
+    L.llda_rank_labels.argtypes = [ctypes.POINTER(LldaRankArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
         raise NativeError("libllda_gibbs.so ABI %d != binding ABI %d" % (L.llda_abi_version(), ABI_VERSION))
     L.llda_struct_size.restype = ctypes.c_int
     L.llda_struct_size.argtypes = [ctypes.c_int]
-    for which, struct in enumerate((LldaLayout, LldaSweepArgs, LldaBatchArgs, LldaFoldinArgs)):
+    for which, struct in enumerate((LldaLayout, LldaSweepArgs, LldaBatchArgs, LldaFoldinArgs, LldaRankArgs)):
         if L.llda_struct_size(which) != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (struct.__name__, ctypes.sizeof(struct),
                                                                            L.llda_struct_size(which)))
@@ -314,6 +323,19 @@ def count_hist(counts, K, lab_mask, mask_per_row, hist, over_val, over_n, over_c
     many values over_val may take (default: all it holds)."""
     _launch(hist, lib().llda_count_hist, "llda_count_hist", _ptr(counts), int(counts.shape[0]), int(K), _ptr(lab_mask), 1 if mask_per_row else 0,
             int(hist.numel()), _ptr(hist), _ptr(over_val), int(over_val.numel() if over_cap is None else over_cap), _ptr(over_n))
+
+
+RANK_NO_POSITIVE, RANK_NO_NEGATIVE, RANK_ONE_THRESHOLD, RANK_ALL_ZERO, RANK_NAN = 1, 2, 4, 8, 16
+RANK_MAX_TOP_N = 16
+
+
+def rank_labels(score, truth, D, K, first, top_n, *, ld=None, top_idx=None, top_val=None, n_thr=None, auc=None, f1=None,
+                hit_rank=None, flags=None):
+    """llda_rank_labels on the current torch stream: score (D, ld) float64 in reference topic order, truth (D, K) uint8 or None;
+    every output tensor may be None."""
+    a = LldaRankArgs(_ptr(score), _ptr(truth), int(D), int(score.stride(0) if ld is None else ld), int(K), int(first), int(top_n), 0,
+                     _ptr(top_idx), _ptr(top_val), _ptr(n_thr), _ptr(auc), _ptr(f1), _ptr(hit_rank), _ptr(flags))
+    _launch(score, lib().llda_rank_labels, "llda_rank_labels", ctypes.byref(a))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

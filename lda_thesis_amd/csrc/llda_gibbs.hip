@@ -32,6 +32,7 @@
 //   kernel_foldin.hpp   llda_foldin_kernel (test-time sampler)
 //   kernel_counts.hpp   llda_commit_log_kernel, llda_apply_delta_kernel, llda_count_init_kernel, self test
 //   kernel_hist.hpp     llda_count_hist_kernel    counts of counts of n_dk / n_kw (the estimate of alpha and beta)
+//   kernel_rank.hpp     llda_rank_labels_kernel   top-n labels and the harness metrics' ingredients from one sort per document
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
@@ -61,6 +62,7 @@
 #include "kernel_foldin.hpp"
 #include "kernel_counts.hpp"
 #include "kernel_hist.hpp"
+#include "kernel_rank.hpp"
 #include "kernel_wide.hpp"
 
 namespace {
@@ -350,6 +352,7 @@ int llda_struct_size(int which)
     case 1: return (int)sizeof(llda_sweep_args);
     case 2: return (int)sizeof(llda_batch_args);
     case 3: return (int)sizeof(llda_foldin_args);
+    case 4: return (int)sizeof(llda_rank_args);
     default: return -1;
     }
 }
@@ -955,6 +958,42 @@ int llda_count_hist(const int32_t *counts, int64_t rows, int32_t K, const uint16
     if (L.T % 4 == 0) hipLaunchKernelGGL(llda_count_hist_kernel<4>, grid, block, 0, st, P);
     else if (L.T == 2) hipLaunchKernelGGL(llda_count_hist_kernel<2>, grid, block, 0, st, P);
     else hipLaunchKernelGGL(llda_count_hist_kernel<1>, grid, block, 0, st, P);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+}
+
+int llda_rank_labels(const llda_rank_args *a, void *stream)
+{
+    if (!a) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->first < 0 || a->first >= a->K || a->ld < a->K || a->top_n < 0 || a->top_n > 16) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->score || a->D > INT64_MAX / a->ld) return LLDA_E_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(a->score) | reinterpret_cast<uintptr_t>(a->top_val) | reinterpret_cast<uintptr_t>(a->auc) |
+         reinterpret_cast<uintptr_t>(a->f1)) & 7)
+        return LLDA_E_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(a->top_idx) | reinterpret_cast<uintptr_t>(a->n_thr) | reinterpret_cast<uintptr_t>(a->hit_rank) |
+         reinterpret_cast<uintptr_t>(a->flags)) & 3)
+        return LLDA_E_BAD_ARG;
+    RankParams P;
+    P.score = a->score; P.truth = a->truth;
+    P.D = a->D; P.ld = a->ld;
+    P.K = a->K; P.first = a->first; P.L = a->K - a->first; P.top_n = a->top_n;
+    P.top_idx = a->top_idx; P.top_val = a->top_val; P.n_thr = a->n_thr; P.auc = a->auc; P.f1 = a->f1;
+    P.hit_rank = a->hit_rank; P.flags = a->flags;
+    int np = 16;
+    while (np < P.L) np <<= 1;                          // (L <= 7688: np <= 8192)
+    const int threads = np / 8 > 256 ? np / 8 : 256, docs = threads / (np / 8);
+    P.n_tiles = (a->D + docs - 1) / docs;
+    const dim3 grid((unsigned)(P.n_tiles < (1 << 20) ? P.n_tiles : (1 << 20))), block((unsigned)threads);
+    hipStream_t st = (hipStream_t)stream;
+    switch (np) {
+#define LLDA_RANK(NP_) case NP_: hipLaunchKernelGGL(llda_rank_labels_kernel<NP_>, grid, block, 0, st, P); break;
+    LLDA_RANK(16) LLDA_RANK(32) LLDA_RANK(64) LLDA_RANK(128) LLDA_RANK(256) LLDA_RANK(512) LLDA_RANK(1024) LLDA_RANK(2048)
+    LLDA_RANK(4096) LLDA_RANK(8192)
+#undef LLDA_RANK
+    default: return LLDA_E_BAD_K;
+    }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LLDA_OK : hip_fail(e);
 }

@@ -23,15 +23,33 @@ def build_parser():
     p.add_option("-a", dest="alpha", type="float", default=0.1, help="alpha prior")
     p.add_option("-b", dest="beta", type="float", default=0.01, help="beta prior")
     p.add_option("-p", action="store_true", dest="pickle", default=False, help="Save the model as pickle?")
+    p.add_option("--device-metrics", action="store_true", dest="device_metrics", default=False,
+                 help="rank the labels and compute the four metrics on the GPU (llda_rank_labels)")
     return p
 
 
-def report(model, test, th, lvl, it, corpus_file):
+def _header(lvl, it, corpus_file):
     print("Model:               Labeled LDA")
     print("Corpus:             ", "Abstracts" if corpus_file == "thesis_data3.csv" else "Full Texts")
     print("Label depth         ", lvl)
     print("# of Gibbs samples: ", int(it))
     print("-----------------------------------")
+
+
+def report_device(model, test, th, lvl, it, corpus_file):
+    """``report`` with the ranking and the per-document metrics on the device (ranking.rank_labels / ranking.metrics): the same
+    lines; equal loads are ranked by label index where numpy's argsort in n_error leaves their order open."""
+    from . import ranking
+    _header(lvl, it, corpus_file)
+    m = ranking.metrics(ranking.rank_labels(th, binary_yreal(test[1], model.labelmap), first=1, top_n=0))
+    print("AUC ROC:                 ", m["auc"])
+    print("one error:               ", m["one_error"])
+    print("two error:               ", m["two_error"])
+    print("F1 score (macro average) ", m["f1"])
+
+
+def report(model, test, th, lvl, it, corpus_file):
+    _header(lvl, it, corpus_file)
     y_bin = binary_yreal(test[1], model.labelmap)[:, 1:]        # the root label is in no label set
     th = th[:, 1:]
     keep = np.where(th.sum(axis=1) != 0)[0]                     # documents not assigned to 'root' entirely
@@ -57,7 +75,7 @@ def main(argv=None):
         pickle.dump(model, open("LabeledLDA_model.pkl", "wb"))
         pickle.dump(test, open("LabeledLDA_testset.pkl", "wb"))
         pickle.dump(th, open("LabeledLDA_theta.pkl", "wb"))
-    report(model, test, th, opt.lvl, opt.it, opt.file)
+    (report_device if opt.device_metrics else report)(model, test, th, opt.lvl, opt.it, opt.file)
 
 
 if __name__ == "__main__":

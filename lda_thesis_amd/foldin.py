@@ -56,6 +56,19 @@ class Pending(object):
         self._keep = None
         return out
 
+    def th_device(self):
+        """the thinned average as a (D, K) float64 tensor ON THE DEVICE, columns in reference topic order: the same status check as
+        ``result()`` (it waits for the launch), one permutation on the device, no copy to the host -- the input of
+        ``ranking.rank_labels``."""
+        with torch.cuda.stream(self.stream):
+            if int(self.status.item()) != 0:
+                raise ValueError("pvals < 0, pvals > 1 or pvals contains NaNs")
+            tp = torch.from_numpy(self.lay.lm_topic_pos.astype(np.int64)).to(self.th.device)
+            th = self.th[:, tp]
+        th.record_stream(torch.cuda.current_stream(th.device))
+        self._keep = None
+        return th
+
 
 def _launch(ph, init_rows, init_idx, doc_tups, *, alpha, beta, it, thinning, seed, stream_id, doc_ids, c_init,
             c_loop, beta_fallback, avg_mode, device=None, stream=None, K_true=None, hold=False):
@@ -110,10 +123,10 @@ def _launch(ph, init_rows, init_idx, doc_tups, *, alpha, beta, it, thinning, see
 # ------------------------------------------------------------------------------------------------
 # LabeledLDA
 # ------------------------------------------------------------------------------------------------
-def fold_in(ph_hat, alpha, doc_tups, it, thinning, seed, stream_id=TEST_STREAM, doc_base=0, device=None):
+def fold_in(ph_hat, alpha, doc_tups, it, thinning, seed, stream_id=TEST_STREAM, doc_base=0, device=None, keep_device=False):
     """LabeledLDA.prep4test + run_test for a batch of doc2bow lists.  ``ph_hat``: (K, V) float64, numpy or a torch
     tensor already on the device (the running mean run_training left there).  Returns dict(th_hat (D, K),
-    n_dk (D, K), z).
+    n_dk (D, K), z); keep_device=True: only th_hat, as a (D, K) tensor that stays on the device (``Pending.th_device``).
 
     prep4test's column normalisation (LabeledLDA.py:159-167: ``probs = ph_hat[:, doc]; probs /= probs.sum(axis=0)``,
     uniform 1/K for a document that holds a column which cannot be normalised) runs on the device: the fancy-indexed
@@ -146,9 +159,10 @@ def fold_in(ph_hat, alpha, doc_tups, it, thinning, seed, stream_id=TEST_STREAM, 
         doc_bad = np.zeros(len(doc_tups), dtype=bool)
         np.logical_or.at(doc_bad, site_doc, bad_h[word])
         init_idx = np.where(doc_bad[site_doc], V, word)
-    return _launch(d_ph, d_init, init_idx, doc_tups, alpha=alpha, beta=0.0, it=it, thinning=thinning, seed=seed,
-                   stream_id=stream_id, doc_ids=np.arange(len(doc_tups)) + doc_base, c_init=1.0000000005,
-                   c_loop=1.0000005, beta_fallback=False, avg_mode=0, device=dev, K_true=K).result()
+    pending = _launch(d_ph, d_init, init_idx, doc_tups, alpha=alpha, beta=0.0, it=it, thinning=thinning, seed=seed,
+                      stream_id=stream_id, doc_ids=np.arange(len(doc_tups)) + doc_base, c_init=1.0000000005,
+                      c_loop=1.0000005, beta_fallback=False, avg_mode=0, device=dev, K_true=K)
+    return pending.th_device() if keep_device else pending.result()
 
 
 # ------------------------------------------------------------------------------------------------
