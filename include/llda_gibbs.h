@@ -496,6 +496,49 @@ typedef struct llda_rank_args {
 #define LLDA_RANK_NAN 16
 int llda_rank_labels(const llda_rank_args *args, void *stream);
 
+/* The n best words of every topic from the counts (additive to ABI 22): what topwords_per_topic (LabeledLDA.py:241-254) asks of
+ * phi, without phi.  phi[k][v] = (n_kw[v][k] + beta) / den[k] is strictly increasing in the integer count for a fixed topic and two
+ * different counts never round to one double (V*beta < 2^40), so the order of a topic's words by phi is their order by count, and
+ * equal phi means equal counts.
+ *   n_kw [V][KP] int32, word-major, device (group-layout) order, 16-byte aligned; 1 <= V <= 2^31 - 1; every layout is taken.
+ *   order    for topic k: n_kw[v][topic_pos[k]] descending, compared as SIGNED int32, then word id ascending --
+ *            np.argsort(-get_phi()[k], kind="stable")
+ *   top_idx  [K][n] int32 word ids, top_cnt [K][n] int32 their counts, both in REFERENCE topic order; entries i >= min(n, V) are
+ *            -1 / 0.  Either may be NULL.
+ * Positions of the padding (pos_topic == -1) are never emitted and influence nothing, whatever they hold.  One bandwidth pass over
+ * V*KP*4 bytes in row chunks of LLDA_TOPW_CHUNK_ROWS words leaves partial lists in `scratch` (device memory, 8-byte aligned, at
+ * least llda_top_words_scratch_bytes(V, K, n) bytes, contents irrelevant before and after), a second small launch merges them per
+ * topic.  Everything is an integer: the outputs do not depend on the geometry.
+ * LLDA_E_BAD_ARG: a NULL n_kw or scratch, n outside 1 .. 16, V < 1, a misaligned pointer, scratch_bytes too small;
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K; both before anything touches HIP.
+ * llda_top_words_scratch_bytes is host only (needs no device) and returns the same codes for the same bad arguments. */
+#define LLDA_TOPW_CHUNK_ROWS 256
+int64_t llda_top_words_scratch_bytes(int64_t V, int32_t K, int32_t n);
+int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t *top_idx, int32_t *top_cnt, void *scratch,
+                   int64_t scratch_bytes, void *stream);
+
+/* Document and co-document frequencies of listed words (additive to ABI 22): the integers of UMass coherence (Mimno et al. 2011)
+ * and of NPMI, over a corpus CSR.
+ *   doc_off [D+1] int64, word [S] int32 with ids in [0, V): a site counts whatever its frequency, a word may repeat in a document.
+ *            doc_off may point into the middle of a longer array (a document range); its entries index `word` as they are.
+ *   memb_off [V+1] int32, memb [M] int32, M = memb_off[V] <= K*n: the entries memb_off[w] .. memb_off[w+1]-1 say which topics list
+ *            word w, each as topic*16 + rank with topic in REFERENCE order and rank < n; their order is unspecified, a word may be
+ *            listed by several topics (entries with topic >= K or rank >= n are ignored).
+ *   co       [K][n][n] unsigned 64-bit.  With R(d, k) = the ranks r for which some site of document d carries a word listed as
+ *            (k, r):  co[k][i][j] += 1 for all i >= j in R(d, k), for every document and topic.  The diagonal is the document
+ *            frequency; entries with j > i are never written.  co ACCUMULATES (the caller zeroes it), so a corpus may be passed
+ *            as several document ranges.  Integer atomics: exact and independent of order and geometry.
+ * One wavefront per document.  A call of fewer than LLDA_COOC_AGG_MIN_DOCS documents launches at most LLDA_COOC_MAX_WAVES
+ * wavefronts, wavefront i takes the documents i, i + LLDA_COOC_MAX_WAVES, ... in turn (its rank masks are cleared in between) and
+ * every set bit and pair is one global atomic.  A larger call counts in LDS per slice of topics and adds every workgroup's counters
+ * to co once, when at most eight slices cover K (else it takes the first form); the integers are the same.
+ * D == 0 is a no-op.  LLDA_E_BAD_ARG: D < 0, V < 1, n outside 1 .. 16, a NULL or misaligned pointer (D > 0);
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K; both before anything touches HIP. */
+#define LLDA_COOC_MAX_WAVES 8192
+#define LLDA_COOC_AGG_MIN_DOCS 32768
+int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64_t V, int32_t K, int32_t n,
+                   const int32_t *memb_off, const int32_t *memb, unsigned long long *co, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

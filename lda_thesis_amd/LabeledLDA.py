@@ -297,11 +297,49 @@ class LabeledLDA(object):
         (reference LabeledLDA.py:256-265); evaluated by the llda_loglik HIP kernel."""
         return self._sampler.perplexity()
 
-    def topwords_per_topic(self, topwords=10):
-        ph = self.get_phi()
+    def topwords_per_topic(self, topwords=10, device=False):
+        """[label, word, word, ...] for every label: reference LabeledLDA.py:241-254, from the downloaded ``get_phi()``.
+        device=True takes the same lists from ``top_words`` (topwords <= 16): 8*K*topwords bytes come back instead of the (K, V)
+        phi.  Ties then go by word id ascending, where the default ``argsort`` here and in the reference leaves the order of
+        equal phi open; without ties the two agree."""
         names = list(self.labelmap.keys())
+        if device:
+            idx, _ = self.top_words(topwords)
+            return [[names[k]] + [self.v_to_w[int(v)] for v in idx[k] if v >= 0] for k in range(self.K)]
+        ph = self.get_phi()
         return [[names[k]] + [self.v_to_w[v] for v in np.argsort(-ph[k, :])[:topwords]]
                 for k in range(self.K)]
+
+    # ---- topic summaries on the device (new): top words by count and their coherence ----
+    def top_words(self, n=10):
+        """The n <= 16 best words of every label: ((K, n) word ids, (K, n) counts) as numpy arrays, ids padded with -1 when
+        V < n.  The order is count descending, then word id ascending: ``np.argsort(-get_phi()[k], kind="stable")[:n]``
+        (``topics.py``).  n_k_v is replicated: no collective."""
+        self._sampler.check_status()
+        idx, cnt = self._sampler.top_words(n)
+        return idx.cpu().numpy(), cnt.cpu().numpy()
+
+    def coherence(self, n=10, measure="umass", docs=None):
+        """Topic coherence of every label's n best words (float64 [K]; NaN for a label with fewer than two words or with a top
+        word that the corpus never holds): measure = "umass" (Mimno et al. 2011) or "npmi", over the training corpus or, with
+        ``docs`` (token lists, through ``dicti.doc2bow``), over that reference corpus.  The document and co-document
+        frequencies are counted on the device (llda_word_cooc).  Over the training corpus COLLECTIVE with several ranks;
+        ``docs`` are counted whole on every rank."""
+        from . import topics
+        if measure not in ("umass", "npmi"):
+            raise ValueError("measure must be 'umass' or 'npmi'")
+        sm = self._sampler
+        sm.check_status()
+        idx, _ = sm.top_words(n)
+        if docs is None:
+            co, D = sm.word_cooccurrence(idx)
+        else:
+            import torch
+            doc_off, word, _ = csr_from_doc_tups([self.dicti.doc2bow(x) for x in docs])
+            co = topics.cooccurrence(torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.int64)).to(sm.device),
+                                     torch.from_numpy(np.ascontiguousarray(word, dtype=np.int32)).to(sm.device), self.V, idx)
+            co, D = co.cpu().numpy(), len(doc_off) - 1
+        return topics.coherence(co, D, measure, listed=idx.cpu().numpy())
 
     # ---- test time (reference LabeledLDA.py:155-212), on the device ----
     def prep4test(self, doc, seed=None, stream_id=None):

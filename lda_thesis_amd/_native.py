@@ -79,7 +79,8 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
-           "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels")
+           "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
+           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc")
 
 _LIB = None
 
@@ -151,6 +152,12 @@ def lib():
     L.llda_readout_theta.argtypes = [_c_p, _c_p, _c_i64, _c_i32, _c_d, _c_i32, _c_d, _c_d, _c_p, _c_p]
     L.llda_rank_labels.restype = ctypes.c_int
     L.llda_rank_labels.argtypes = [ctypes.POINTER(LldaRankArgs), _c_p]
+    L.llda_top_words_scratch_bytes.restype = _c_i64
+    L.llda_top_words_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
+    L.llda_top_words.restype = ctypes.c_int
+    L.llda_top_words.argtypes = [_c_p, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i64, _c_p]
+    L.llda_word_cooc.restype = ctypes.c_int
+    L.llda_word_cooc.argtypes = [_c_p, _c_p, _c_i64, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -336,6 +343,36 @@ def rank_labels(score, truth, D, K, first, top_n, *, ld=None, top_idx=None, top_
     a = LldaRankArgs(_ptr(score), _ptr(truth), int(D), int(score.stride(0) if ld is None else ld), int(K), int(first), int(top_n), 0,
                      _ptr(top_idx), _ptr(top_val), _ptr(n_thr), _ptr(auc), _ptr(f1), _ptr(hit_rank), _ptr(flags))
     _launch(score, lib().llda_rank_labels, "llda_rank_labels", ctypes.byref(a))
+
+
+TOPW_MAX_N = 16
+TOPW_CHUNK_ROWS = 256   # LLDA_TOPW_CHUNK_ROWS: llda_top_words cuts the vocabulary into chunks of so many words
+COOC_MAX_WAVES = 8192   # LLDA_COOC_MAX_WAVES: wavefront i of llda_word_cooc takes the documents i, i + 8192, ... in turn ...
+COOC_AGG_MIN_DOCS = 32768   # ... LLDA_COOC_AGG_MIN_DOCS: in calls of fewer documents; larger calls count in LDS first
+
+
+def top_words_scratch_bytes(V, K, n):
+    """llda_top_words_scratch_bytes: bytes of work space llda_top_words needs (host only)."""
+    r = int(lib().llda_top_words_scratch_bytes(int(V), int(K), int(n)))
+    if r < 0:
+        check(r, "llda_top_words_scratch_bytes(V=%d, K=%d, n=%d)" % (V, K, n))
+    return r
+
+
+def top_words(n_kw, V, K, n, top_idx, top_cnt, scratch):
+    """llda_top_words on the current torch stream: top_idx / top_cnt (K, n) int32 (either may be None) = the n words of every
+    topic with the largest counts in n_kw (int32 (V, KP), device order), ties by word id ascending; scratch = a uint8 tensor of
+    top_words_scratch_bytes(V, K, n) bytes."""
+    _launch(n_kw, lib().llda_top_words, "llda_top_words", _ptr(n_kw), int(V), int(K), int(n), _ptr(top_idx), _ptr(top_cnt),
+            _ptr(scratch), int(scratch.numel() * scratch.element_size()))
+
+
+def word_cooc(doc_off, word, D, V, K, n, memb_off, memb, co):
+    """llda_word_cooc on the current torch stream: co (int64 (K, n, n), accumulates) += the document and co-document frequencies
+    of the words the membership table (memb_off int32 [V+1], memb int32 [M] of topic*16 + rank) lists, over the D documents of
+    the CSR doc_off (int64, at least D+1 entries) / word (int32)."""
+    _launch(co, lib().llda_word_cooc, "llda_word_cooc", _ptr(doc_off), _ptr(word), int(D), int(V), int(K), int(n), _ptr(memb_off),
+            _ptr(memb), _ptr(co))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

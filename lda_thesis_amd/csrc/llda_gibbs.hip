@@ -34,6 +34,8 @@
 //   kernel_hist.hpp     llda_count_hist_kernel    counts of counts of n_dk / n_kw (the estimate of alpha and beta)
 //   kernel_rank.hpp     llda_rank_labels_kernel   top-n labels and the harness metrics' ingredients from one sort per document
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
+//   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
+//   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -64,6 +66,8 @@
 #include "kernel_hist.hpp"
 #include "kernel_rank.hpp"
 #include "kernel_wide.hpp"
+#include "kernel_topwords.hpp"
+#include "kernel_cooc.hpp"
 
 namespace {
 
@@ -994,6 +998,106 @@ int llda_rank_labels(const llda_rank_args *a, void *stream)
 #undef LLDA_RANK
     default: return LLDA_E_BAD_K;
     }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+}
+
+// the geometry of llda_top_words: row phases of a workgroup, workgroups across a row, partial lists per column
+static void topw_geometry(const llda_layout &L, int64_t V, int32_t &rpb, int32_t &col_blocks, int64_t &chunks)
+{
+    const int cpr = L.KP / 4;
+    rpb = 256 / cpr;
+    if (rpb < 1) rpb = 1;
+    if (rpb > TOPW_MAX_PHASES) rpb = TOPW_MAX_PHASES;
+    col_blocks = (cpr + 255) / 256;
+    chunks = (V + LLDA_TOPW_CHUNK_ROWS - 1) / LLDA_TOPW_CHUNK_ROWS;
+}
+
+int64_t llda_top_words_scratch_bytes(int64_t V, int32_t K, int32_t n)
+{
+    if (V < 1 || V > INT32_MAX || n < 1 || n > 16) return LLDA_E_BAD_ARG;
+    int rc;
+    const llda_layout *Lp = layout_of(K, &rc);
+    if (rc) return rc;
+    int32_t rpb, col_blocks;
+    int64_t chunks;
+    topw_geometry(*Lp, V, rpb, col_blocks, chunks);
+    return chunks * rpb * Lp->KP * n * (int64_t)sizeof(uint64_t);
+}
+
+int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t *top_idx, int32_t *top_cnt, void *scratch,
+                   int64_t scratch_bytes, void *stream)
+{
+    if (!n_kw || !scratch || V < 1 || V > INT32_MAX || n < 1 || n > 16) return LLDA_E_BAD_ARG;
+    int rc;
+    const llda_layout *Lp = layout_of(K, &rc);
+    if (rc) return rc;
+    const llda_layout &L = *Lp;
+    if ((reinterpret_cast<uintptr_t>(n_kw) & 15) || (reinterpret_cast<uintptr_t>(scratch) & 7) ||
+        ((reinterpret_cast<uintptr_t>(top_idx) | reinterpret_cast<uintptr_t>(top_cnt)) & 3))
+        return LLDA_E_BAD_ARG;
+    TopwParams P;
+    memset(&P, 0, sizeof P);
+    int32_t col_blocks;
+    int64_t chunks;
+    topw_geometry(L, V, P.rpb, col_blocks, chunks);
+    P.parts = chunks * P.rpb;
+    if (scratch_bytes < P.parts * L.KP * n * (int64_t)sizeof(uint64_t)) return LLDA_E_BAD_ARG;
+    P.n_kw = reinterpret_cast<const int4 *>(n_kw);
+    P.V = V; P.cpr = L.KP / 4; P.n = n; P.KP = L.KP; P.G = L.G; P.T = L.T; P.K = L.K;
+    P.scratch = static_cast<uint64_t *>(scratch);
+    P.top_idx = top_idx; P.top_cnt = top_cnt;
+    for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { P.leaf_start[p] = L.leaf_start[p]; P.leaf_len[p] = L.leaf_len[p]; }
+    const dim3 grid((unsigned)chunks, (unsigned)col_blocks), merge_grid((unsigned)L.KP);
+    hipStream_t st = (hipStream_t)stream;
+#define LLDA_TOPW(N_) { hipLaunchKernelGGL(llda_top_words_kernel<N_>, grid, dim3(256), 0, st, P); \
+                        hipLaunchKernelGGL(llda_top_words_merge_kernel<N_>, merge_grid, dim3(64), 0, st, P); }
+    if (n <= 2) LLDA_TOPW(2)
+    else if (n <= 4) LLDA_TOPW(4)
+    else if (n <= 8) LLDA_TOPW(8)
+    else if (n <= 10) LLDA_TOPW(10)
+    else LLDA_TOPW(16)
+#undef LLDA_TOPW
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+}
+
+int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64_t V, int32_t K, int32_t n,
+                   const int32_t *memb_off, const int32_t *memb, unsigned long long *co, void *stream)
+{
+    if (D < 0 || V < 1 || V > INT32_MAX || n < 1 || n > 16) return LLDA_E_BAD_ARG;
+    if (K < 1 || K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (D == 0) return LLDA_OK;
+    if (!doc_off || !word || !memb_off || !memb || !co) return LLDA_E_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(doc_off) | reinterpret_cast<uintptr_t>(co)) & 7) return LLDA_E_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(word) | reinterpret_cast<uintptr_t>(memb_off) | reinterpret_cast<uintptr_t>(memb)) & 3)
+        return LLDA_E_BAD_ARG;
+    CoocParams P;
+    P.doc_off = doc_off; P.word = word; P.memb_off = memb_off; P.memb = memb; P.co = co;
+    P.D = D; P.V = V; P.K = K; P.n = n; P.words = (K + 1) / 2;
+    P.np = n * (n + 1) / 2; P.ks = 0;
+    hipStream_t st = (hipStream_t)stream;
+    // a large corpus: counters per slice of topics in LDS, when few slices cover K (kernel_cooc.hpp)
+    const int ks_max = (COOC_AGG_LDS_WORDS / (P.np + 2)) & ~1;
+    const int slices = (K + ks_max - 1) / ks_max;
+    if (D >= LLDA_COOC_AGG_MIN_DOCS && slices <= COOC_AGG_MAX_SLICES) {
+        P.ks = ((K + slices - 1) / slices + 1) & ~1;                         // even: two topics share a mask word
+        const size_t lds = ((size_t)P.ks * P.np + (size_t)COOC_WAVES * (P.ks / 2)) * sizeof(uint32_t);
+        const int rl = allow_lds(llda_word_cooc_agg_kernel, lds);
+        if (rl) return rl;
+        int64_t bx = (D + COOC_WAVES - 1) / COOC_WAVES;
+        const int64_t cap = COOC_AGG_BLOCKS / slices > 1 ? COOC_AGG_BLOCKS / slices : 1;
+        if (bx > cap) bx = cap;
+        hipLaunchKernelGGL(llda_word_cooc_agg_kernel, dim3((unsigned)bx, (unsigned)slices), dim3(64 * COOC_WAVES), lds, st, P);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    }
+    const size_t lds = (size_t)COOC_WAVES * P.words * sizeof(uint32_t);      // at most 61 504 bytes
+    const int rl = allow_lds(llda_word_cooc_kernel, lds);
+    if (rl) return rl;
+    int64_t blocks = (D + COOC_WAVES - 1) / COOC_WAVES;
+    if (blocks > LLDA_COOC_MAX_WAVES / COOC_WAVES) blocks = LLDA_COOC_MAX_WAVES / COOC_WAVES;
+    hipLaunchKernelGGL(llda_word_cooc_kernel, dim3((unsigned)blocks), dim3(64 * COOC_WAVES), lds, st, P);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LLDA_OK : hip_fail(e);
 }

@@ -25,7 +25,23 @@ def build_parser():
     p.add_option("-p", action="store_true", dest="pickle", default=False, help="Save the model as pickle?")
     p.add_option("--device-metrics", action="store_true", dest="device_metrics", default=False,
                  help="rank the labels and compute the four metrics on the GPU (llda_rank_labels)")
+    p.add_option("--coherence", dest="coherence", type="int", default=0, metavar="N",
+                 help="after the report: UMass coherence of every label's N best words over the training corpus (llda_top_words, "
+                      "llda_word_cooc), its mean and the five worst labels")
     return p
+
+
+def report_coherence(model, n):
+    """mean UMass coherence of the labels' n best words and the five least coherent labels with those words"""
+    idx, _ = model.top_words(n)
+    coh = model.coherence(n, "umass")
+    names = list(model.labelmap.keys())
+    ok = np.flatnonzero(~np.isnan(coh))
+    print("-----------------------------------")
+    print("UMass coherence (top %d words), mean over %d of %d labels: " % (n, ok.shape[0], len(names)),
+          np.mean(coh[ok]) if ok.shape[0] else float("nan"))
+    for k in ok[np.argsort(coh[ok], kind="stable")[:5]]:
+        print("  %-24s %10.3f  %s" % (names[k], coh[k], " ".join(model.v_to_w[int(v)] for v in idx[k] if v >= 0)))
 
 
 def _header(lvl, it, corpus_file):
@@ -76,6 +92,8 @@ def main(argv=None):
         pickle.dump(test, open("LabeledLDA_testset.pkl", "wb"))
         pickle.dump(th, open("LabeledLDA_theta.pkl", "wb"))
     (report_device if opt.device_metrics else report)(model, test, th, opt.lvl, opt.it, opt.file)
+    if opt.coherence:
+        report_coherence(model, opt.coherence)
 
 
 if __name__ == "__main__":

@@ -947,6 +947,26 @@ class GibbsSampler(object):
         over_dk = np.sort(np.concatenate([slots[r, 1:1 + int(slots[r, 0])] for r in range(world)]))
         return (host[:n_bins].copy(), over_dk, kw_host[:n_bins].copy(), np.sort(over_kw[:n_over_kw].cpu().numpy().astype(np.int64)))
 
+    # ------------------------------------------------------------------ topic summaries
+    def top_words(self, n):
+        """the n best words of every topic by count (``topics.top_words`` on this sampler's n_kw): device tensors (top_idx, top_cnt),
+        (K, n) int32 in reference topic order.  n_kw is replicated on every rank: no collective."""
+        from . import topics
+        return topics.top_words(self.n_kw, self.K, n)
+
+    def word_cooccurrence(self, top_idx):
+        """document and co-document frequencies of the words of ``top_idx`` (K, n) over this sampler's documents (``topics.cooccurrence``):
+        (co, D_total), co an int64 (K, n, n) numpy array.  COLLECTIVE with several ranks: ONE int64 SUM all-reduce of the K*n*n counts
+        plus the local number of documents -- a size that depends on K and n only --, so every rank returns the same pair."""
+        from . import topics
+        co = topics.cooccurrence(self.doc_off, self.word, self.V, top_idx)
+        buf = torch.cat([co.reshape(-1), torch.tensor([self.D], dtype=torch.int64, device=self.device)])
+        if self.sharded and _dist_active(self.group):
+            import torch.distributed as dist
+            dist.all_reduce(buf, group=self.group)
+        host = buf.cpu().numpy()
+        return host[:-1].reshape(tuple(co.shape)).copy(), int(host[-1])
+
     # ------------------------------------------------------------------ read-outs
     def loglik_sum(self):
         """sum over local sites of -log(phi[:, w] . theta_d)  (LabeledLDA.py:256-265), on device."""
