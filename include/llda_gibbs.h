@@ -227,7 +227,7 @@ int         llda_build_info(void);
 const char *llda_strerror(int code);
 int         llda_last_hip_error(void);
 /* sizeof of the argument structs as the library was compiled (0 llda_layout, 1 llda_sweep_args, 2 llda_batch_args,
- * 3 llda_foldin_args, 4 llda_rank_args): a binding checks its own struct definitions against it once, at load time. */
+ * 3 llda_foldin_args, 4 llda_rank_args, 5 llda_heldout_args): a binding checks its own struct definitions against it once, at load time. */
 int         llda_struct_size(int which);
 /* Fill *out for K topics.  Mirrors numpy's pairwise-sum recursion (np.sum at LabeledLDA.py:117). */
 int         llda_layout_init(int32_t K, llda_layout *out);
@@ -538,6 +538,42 @@ int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t
 #define LLDA_COOC_AGG_MIN_DOCS 32768
 int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64_t V, int32_t K, int32_t n,
                    const int32_t *memb_off, const int32_t *memb, unsigned long long *co, void *stream);
+
+/* Per-document likelihood of held-out sites (additive to ABI 22): the scored half of document completion.
+ *   doc_off [D+1] int64, word [S] int32, freq [S] int32 or NULL (= all 1; 0 <= f < 2^23): the sites to score, a CSR;
+ *   theta [D][ld_theta] doubles, phi_t [V][ld_phi] doubles, word-major; both row-major in REFERENCE topic order (column = topic id,
+ *   not a group layout), ld_* >= K the row strides.  Columns >= K are never read.
+ * A value is a pair (m, e), m in [0.5, 1), meaning m * 2^e; 1.0 is (0.5, 1).  mul((a, ea), (b, eb)): c = a*b; c < 0.5: c = 2c and the
+ * exponent drops by one; result (c, ea + eb [- 1]).  Every operation is one IEEE float64 operation, rounded on its own.
+ *   site     64 partial sums part[j] = sum_{i = 0, 1, ...; j + 64i < K} theta[d][j+64i] * phi_t[w][j+64i], each product rounded, added
+ *            in increasing i from +0.0; then for s = 1, 2, 4, 8, 16, 32: part[j] = part[j] + part[j xor s] for every j at once;
+ *            p = part[0].  (m, e) = frexp(p); p^f by right-to-left binary exponentiation: acc = (0.5, 1), base = (m, e); for every
+ *            bit of f from the lowest: bit set: acc = mul(acc, base); then base = mul(base, base).
+ *   document start from (0.5, 1) and mul the sites' p^f in ascending site index; tok += f.  A site whose p is not a finite positive
+ *            number (or whose word id is outside [0, V): it is never used as an index) is left out of the product and of tok and
+ *            adds f to bad.
+ *   mant [D] double, expo [D] int64: the document's likelihood mant * 2^expo; tok [D] int64, bad [D] int64.  Each may be NULL.
+ * The host takes the logarithm: log(mant) + expo * ln 2.  A document's outputs depend on its own inputs only -- not on D, its place
+ * in the batch or the geometry -- and equal the restatement in tests/heldoutref.py bit for bit.
+ * One wavefront per document for K > 32 (theta in registers up to K = 1024, re-read beyond), a group of 8, 16 or 32 >= K lanes for
+ * K <= 32 (zero partials add exactly: the same bits).  D == 0 is a no-op.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: D < 0, V outside 1 .. 2^31 - 1, ld < K, a NULL doc_off, word, theta or
+ * phi_t (D > 0), a misaligned pointer.  Both before anything touches HIP. */
+typedef struct llda_heldout_args {
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S] or NULL                                            */
+    const double  *theta;        /* [dev] [D][ld_theta]                                          */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    int64_t  D, V, ld_theta, ld_phi;
+    int32_t  K, reserved;
+    double  *mant;               /* [dev] [D] or NULL                                            */
+    int64_t *expo;               /* [dev] [D] or NULL                                            */
+    int64_t *tok;                /* [dev] [D] or NULL                                            */
+    int64_t *bad;                /* [dev] [D] or NULL                                            */
+} llda_heldout_args;
+#define LLDA_HELDOUT_MAX_FREQ 8388607
+int llda_heldout_loglik(const llda_heldout_args *args, void *stream);
 
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds

@@ -11,7 +11,8 @@ What differs from the reference:
     materialise them on the host in the reference's shapes and dtypes (LabeledLDA.py:73-79);
   * ``perplexity()`` (LabeledLDA.py:256-265) and the test-time fold-in sampler run on the device;
   * new, off by default: ``optimize_priors()`` and ``run_training(..., optimize_interval=n)`` fit alpha and beta to the counts while
-    training (the reference fixes both); ``prior_trace`` records the fitted values.
+    training (the reference fixes both); ``prior_trace`` records the fitted values;
+  * new: ``heldout_perplexity()`` scores unseen documents by document completion on the device (``heldout.py``).
 Text preparation uses ``lda_thesis_amd.text`` instead of gensim (not installable here).
 """
 import csv
@@ -398,6 +399,46 @@ class LabeledLDA(object):
         from .evaluate import binary_yreal
         th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
         return ranking.metrics(ranking.rank_labels(th, binary_yreal(labels, self.labelmap), first=1, top_n=0))
+
+    # ---- held-out perplexity by document completion (new; heldout.py) ----
+    def heldout_perplexity(self, newdocs, it, thinning, weighted=True, seed=None, stream_id=None, scored_docs=None):
+        """How well the trained model predicts unseen text: dict(perplexity, loglik, tokens, documents, skipped).
+        Every held-out token list goes through ``dicti.doc2bow``; its sites 0, 2, 4, ... are folded in exactly as ``run_test`` folds
+        documents in (same seed and stream conventions, document ids 0, 1, ... over the documents that are kept), the loads are
+        smoothed with the observed tokens W_d -- theta = (W_d th + alpha) / (W_d + K alpha) -- and the sites 1, 3, 5, ... are scored:
+        perplexity = exp(-sum f log(theta_d . ph_hat[:, w]) / sum f).  ``scored_docs`` (token lists, one per document): ``newdocs``
+        are observed whole and these are scored instead of the parity split.  weighted=False counts every scored site once, the
+        convention of ``perplexity()`` (W_d stays the observed tokens).  Documents without an in-vocabulary word to observe are
+        dropped and counted as ``skipped``; a document with nothing to score contributes no tokens.  perplexity is inf when a scored
+        site has no finite positive probability, nan when no token was scored.
+        ``ph_hat`` and the loads stay on the device (llda_foldin, llda_heldout_loglik); 32 bytes per document come back.  The
+        documents are scored whole on every rank: no collective."""
+        import torch
+        from . import heldout
+        from .foldin import TEST_STREAM, fold_in
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        if scored_docs is None:
+            observed, scored = heldout.completion_split(tups)
+        else:
+            if len(scored_docs) != len(tups):
+                raise ValueError("scored_docs must hold one token list per document of newdocs")
+            observed, scored = tups, [self.dicti.doc2bow(x) for x in scored_docs]
+        keep = [d for d, t in enumerate(observed) if t]
+        skipped = len(tups) - len(keep)
+        if not keep:
+            return dict(perplexity=float("nan"), loglik=0.0, tokens=0, documents=0, skipped=skipped)
+        observed, scored = [observed[d] for d in keep], [scored[d] for d in keep]
+        ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
+        th = fold_in(ph, self.alpha, observed, it, thinning, self.seed if seed is None else seed,
+                     TEST_STREAM if stream_id is None else stream_id, keep_device=True)
+        dev = th.device
+        w_obs = torch.from_numpy(heldout.observed_tokens(observed)).to(dev)
+        theta = heldout.smooth_theta(th, w_obs, float(self.alpha))
+        ph_dev = ph.to(device=dev, dtype=torch.float64) if isinstance(ph, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(ph, dtype=np.float64)).to(dev)
+        doc_off, word, freq = csr_from_doc_tups(scored)
+        r = heldout.perplexity_from(*heldout.loglik(theta, ph_dev.t().contiguous(), doc_off, word, freq, weighted=weighted))
+        return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped)
 
     # ---- pickling: pull the device state to the host (evaluate_LabeledLDA.py:142-145 pickles the model)
     def __getstate__(self):

@@ -75,12 +75,19 @@ class LldaRankArgs(ctypes.Structure):
                 ("f1", _c_p), ("hit_rank", _c_p), ("flags", _c_p)]
 
 
+class LldaHeldoutArgs(ctypes.Structure):
+    """struct llda_heldout_args (include/llda_gibbs.h)."""
+    _fields_ = [("doc_off", _c_p), ("word", _c_p), ("freq", _c_p), ("theta", _c_p), ("phi_t", _c_p), ("D", _c_i64), ("V", _c_i64),
+                ("ld_theta", _c_i64), ("ld_phi", _c_i64), ("K", _c_i32), ("reserved", _c_i32), ("mant", _c_p), ("expo", _c_p),
+                ("tok", _c_p), ("bad", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
            "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
-           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc")
+           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik")
 
 _LIB = None
 
@@ -158,13 +165,15 @@ def lib():
     L.llda_top_words.argtypes = [_c_p, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i64, _c_p]
     L.llda_word_cooc.restype = ctypes.c_int
     L.llda_word_cooc.argtypes = [_c_p, _c_p, _c_i64, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]
+    L.llda_heldout_loglik.restype = ctypes.c_int
+    L.llda_heldout_loglik.argtypes = [ctypes.POINTER(LldaHeldoutArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
         raise NativeError("libllda_gibbs.so ABI %d != binding ABI %d" % (L.llda_abi_version(), ABI_VERSION))
     L.llda_struct_size.restype = ctypes.c_int
     L.llda_struct_size.argtypes = [ctypes.c_int]
-    for which, struct in enumerate((LldaLayout, LldaSweepArgs, LldaBatchArgs, LldaFoldinArgs, LldaRankArgs)):
+    for which, struct in enumerate((LldaLayout, LldaSweepArgs, LldaBatchArgs, LldaFoldinArgs, LldaRankArgs, LldaHeldoutArgs)):
         if L.llda_struct_size(which) != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (struct.__name__, ctypes.sizeof(struct),
                                                                            L.llda_struct_size(which)))
@@ -373,6 +382,19 @@ def word_cooc(doc_off, word, D, V, K, n, memb_off, memb, co):
     the CSR doc_off (int64, at least D+1 entries) / word (int32)."""
     _launch(co, lib().llda_word_cooc, "llda_word_cooc", _ptr(doc_off), _ptr(word), int(D), int(V), int(K), int(n), _ptr(memb_off),
             _ptr(memb), _ptr(co))
+
+
+HELDOUT_MAX_FREQ = 2 ** 23 - 1   # LLDA_HELDOUT_MAX_FREQ
+
+
+def heldout_loglik(doc_off, word, freq, theta, phi_t, D, V, K, *, ld_theta=None, ld_phi=None, mant=None, expo=None, tok=None, bad=None):
+    """llda_heldout_loglik on the current torch stream: doc_off (int64 [D+1]), word (int32 [S]), freq (int32 [S] or None = all 1)
+    the sites to score; theta (D, ld_theta) and phi_t (V, ld_phi) float64 in reference topic order; mant (float64 [D]), expo, tok, bad
+    (int64 [D]) the outputs, each may be None."""
+    a = LldaHeldoutArgs(_ptr(doc_off), _ptr(word), _ptr(freq), _ptr(theta), _ptr(phi_t), int(D), int(V),
+                        int(theta.stride(0) if ld_theta is None else ld_theta), int(phi_t.stride(0) if ld_phi is None else ld_phi),
+                        int(K), 0, _ptr(mant), _ptr(expo), _ptr(tok), _ptr(bad))
+    _launch(theta, lib().llda_heldout_loglik, "llda_heldout_loglik", ctypes.byref(a))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

@@ -36,6 +36,7 @@
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
 //   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
+//   kernel_heldout.hpp  llda_heldout_wave_kernel, _wide_kernel, _group_kernel   per-document likelihood of held-out sites as (mantissa, exponent)
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -68,6 +69,7 @@
 #include "kernel_wide.hpp"
 #include "kernel_topwords.hpp"
 #include "kernel_cooc.hpp"
+#include "kernel_heldout.hpp"
 
 namespace {
 
@@ -357,6 +359,7 @@ int llda_struct_size(int which)
     case 2: return (int)sizeof(llda_batch_args);
     case 3: return (int)sizeof(llda_foldin_args);
     case 4: return (int)sizeof(llda_rank_args);
+    case 5: return (int)sizeof(llda_heldout_args);
     default: return -1;
     }
 }
@@ -1098,6 +1101,47 @@ int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64
     int64_t blocks = (D + COOC_WAVES - 1) / COOC_WAVES;
     if (blocks > LLDA_COOC_MAX_WAVES / COOC_WAVES) blocks = LLDA_COOC_MAX_WAVES / COOC_WAVES;
     hipLaunchKernelGGL(llda_word_cooc_kernel, dim3((unsigned)blocks), dim3(64 * COOC_WAVES), lds, st, P);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+}
+
+int llda_heldout_loglik(const llda_heldout_args *a, void *stream)
+{
+    if (!a) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->ld_theta < a->K || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->theta || !a->phi_t) return LLDA_E_BAD_ARG;
+    if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(a->doc_off) | reinterpret_cast<uintptr_t>(a->theta) | reinterpret_cast<uintptr_t>(a->phi_t) |
+         reinterpret_cast<uintptr_t>(a->mant) | reinterpret_cast<uintptr_t>(a->expo) | reinterpret_cast<uintptr_t>(a->tok) |
+         reinterpret_cast<uintptr_t>(a->bad)) & 7)
+        return LLDA_E_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(a->word) | reinterpret_cast<uintptr_t>(a->freq)) & 3) return LLDA_E_BAD_ARG;
+    HeldoutParams P;
+    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.theta = a->theta; P.phi_t = a->phi_t;
+    P.D = a->D; P.V = a->V; P.ld_theta = a->ld_theta; P.ld_phi = a->ld_phi; P.K = a->K;
+    P.mant = a->mant; P.expo = a->expo; P.tok = a->tok; P.bad = a->bad;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(64 * HELDOUT_WAVES);
+    const int K = a->K;
+    if (K <= 32) {
+        const int G = K <= 8 ? 8 : K <= 16 ? 16 : 32, docs = 64 * HELDOUT_WAVES / G;
+        const int64_t n_tiles = (a->D + docs - 1) / docs;
+        const dim3 grid((unsigned)(n_tiles < (1 << 20) ? n_tiles : (1 << 20)));
+        if (G == 8) hipLaunchKernelGGL(llda_heldout_group_kernel<8>, grid, block, 0, st, P, n_tiles);
+        else if (G == 16) hipLaunchKernelGGL(llda_heldout_group_kernel<16>, grid, block, 0, st, P, n_tiles);
+        else hipLaunchKernelGGL(llda_heldout_group_kernel<32>, grid, block, 0, st, P, n_tiles);
+    } else {
+        const int64_t blocks = (a->D + HELDOUT_WAVES - 1) / HELDOUT_WAVES;
+        const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));
+        if (K <= 64) hipLaunchKernelGGL((llda_heldout_wave_kernel<1, 4>), grid, block, 0, st, P);
+        else if (K <= 128) hipLaunchKernelGGL((llda_heldout_wave_kernel<2, 4>), grid, block, 0, st, P);
+        else if (K <= 256) hipLaunchKernelGGL((llda_heldout_wave_kernel<4, 4>), grid, block, 0, st, P);
+        else if (K <= 512) hipLaunchKernelGGL((llda_heldout_wave_kernel<8, 4>), grid, block, 0, st, P);
+        else if (K <= 1024) hipLaunchKernelGGL((llda_heldout_wave_kernel<16, 2>), grid, block, 0, st, P);
+        else hipLaunchKernelGGL(llda_heldout_wide_kernel, grid, block, 0, st, P);
+    }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LLDA_OK : hip_fail(e);
 }

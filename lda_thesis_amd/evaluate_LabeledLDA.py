@@ -28,7 +28,20 @@ def build_parser():
     p.add_option("--coherence", dest="coherence", type="int", default=0, metavar="N",
                  help="after the report: UMass coherence of every label's N best words over the training corpus (llda_top_words, "
                       "llda_word_cooc), its mean and the five worst labels")
+    p.add_option("--heldout-perplexity", action="store_true", dest="heldout_perplexity", default=False,
+                 help="after the report: perplexity of the held-out documents by document completion (every second word of a "
+                      "document folded in, the others scored on the GPU: llda_heldout_loglik)")
     return p
+
+
+def report_heldout(model, test, it, thinning):
+    """held-out perplexity of the test documents (the words the model knows, as test_it folds them in) by document completion"""
+    known = set(model.vocab)
+    r = model.heldout_perplexity([[x for x in doc if x in known] for doc in test[0]], it, thinning)
+    print("-----------------------------------")
+    print("Held-out perplexity (document completion): ", r["perplexity"])
+    print("  scored tokens %d in %d documents (%d skipped), log-likelihood %s" % (r["tokens"], r["documents"], r["skipped"], r["loglik"]))
+    return r
 
 
 def report_coherence(model, n):
@@ -94,6 +107,8 @@ def main(argv=None):
     (report_device if opt.device_metrics else report)(model, test, th, opt.lvl, opt.it, opt.file)
     if opt.coherence:
         report_coherence(model, opt.coherence)
+    if opt.heldout_perplexity:
+        report_heldout(model, test, opt.it, opt.thinning)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,118 @@
+"""Held-out perplexity by document completion, scored on the device (``llda_heldout_loglik``, include/llda_gibbs.h).
+
+How well does a trained model predict text it has not seen?  The reference has no such number (its ``perplexity`` scores the
+training corpus, /root/reference/LabeledLDA.py:256-265), so the definition is this project's:
+
+  * a held-out document is its ``doc2bow`` list, word ids ascending; the sites 0, 2, 4, ... are OBSERVED, the sites 1, 3, 5, ...
+    SCORED (``completion_split``), or the caller brings its own two lists;
+  * the observed halves go through the fold-in as they are (``foldin.fold_in``); its thinned average ``th`` is smoothed with the
+    observed tokens W_d:  theta[d][k] = (W_d * th[d][k] + alpha) / (W_d + K * alpha)   (``smooth_theta``: IEEE float64, every
+    operation rounded on its own);
+  * a scored site (w, f) has p = sum_k theta[d][k] * phi[k][w]; perplexity = exp(-sum f log p / sum f).
+
+The kernel leaves per document the product of its p^f as a pair (mantissa in [0.5, 1), 64-bit exponent), the scored tokens and the
+tokens of sites whose p was not a finite positive number: 32 bytes come back per document, and the host takes the logarithm.
+"""
+import math
+
+import numpy as np
+
+from . import _native
+
+MAX_FREQ = _native.HELDOUT_MAX_FREQ
+
+
+def completion_split(doc_tups):
+    """doc2bow lists -> (observed, scored): the sites 0, 2, 4, ... and 1, 3, 5, ... of every document.  A document with one site
+    has nothing scored, an empty one nothing at all."""
+    return [list(t[0::2]) for t in doc_tups], [list(t[1::2]) for t in doc_tups]
+
+
+def observed_tokens(doc_tups):
+    """W_d: the sum of the frequencies of every document, float64 [D] (exact integers)."""
+    return np.array([float(sum(int(f) for _, f in t)) for t in doc_tups], dtype=np.float64)
+
+
+def smooth_theta(th, w_obs, alpha):
+    """(W_d * th + alpha) / (W_d + K * alpha) with th (D, K) and W_d [D]: numpy arrays, or torch tensors on one device -- the same
+    IEEE operations in the same order either way (a product, a sum, a product and a sum of scalars, a division)."""
+    K = th.shape[1]
+    return (w_obs[:, None] * th + alpha) / (w_obs + K * alpha)[:, None]
+
+
+def loglik(theta_dev, phi_t_dev, doc_off, word, freq, weighted=True):
+    """Score the sites of the CSR doc_off (int64 [D+1]) / word / freq (numpy arrays or device tensors) against theta_dev (D, K) and
+    phi_t_dev (V, K), float64 tensors on the device in reference topic order (any row stride >= K).  weighted=False: every
+    frequency counts as 1.  Returns the per-document (mant, expo, tok, bad) as numpy arrays: float64, int64, int64, int64."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    for name, x in (("theta", theta_dev), ("phi_t", phi_t_dev)):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 2):
+            raise ValueError("%s must be a two-dimensional float64 tensor on the device" % name)
+    dev = theta_dev.device
+    if phi_t_dev.device != dev:
+        raise ValueError("theta and phi_t live on different devices")
+    D, K = int(theta_dev.shape[0]), int(theta_dev.shape[1])
+    V = int(phi_t_dev.shape[0])
+    if int(phi_t_dev.shape[1]) != K:
+        raise ValueError("theta has %d topics, phi_t %d" % (K, int(phi_t_dev.shape[1])))
+
+    def rows(x):
+        return x.contiguous() if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < K) else x
+
+    def on_dev(a, dt):
+        if isinstance(a, torch.Tensor):
+            return a.to(device=dev, dtype=dt).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device=dev, dtype=dt)
+
+    theta_dev, phi_t_dev = rows(theta_dev), rows(phi_t_dev)
+    off_h = doc_off.cpu().numpy() if isinstance(doc_off, torch.Tensor) else np.asarray(doc_off, dtype=np.int64)
+    if off_h.shape != (D + 1,) or (D and (int(off_h[0]) < 0 or np.any(np.diff(off_h) < 0))):
+        raise ValueError("doc_off must hold D + 1 = %d ascending offsets" % (D + 1))
+    S = int(off_h[-1]) if D else 0
+    d_off, d_word = on_dev(doc_off, torch.int64), on_dev(word, torch.int32)
+    if int(d_word.numel()) == 0:
+        d_word = torch.zeros((1,), dtype=torch.int32, device=dev)      # (no site at all: the pointer must still be one)
+    if int(d_word.numel()) < S:
+        raise ValueError("word holds %d sites, doc_off asks for %d" % (int(d_word.numel()), S))
+    if S and (int(d_word[:S].min()) < 0 or int(d_word[:S].max()) >= V):
+        raise ValueError("word ids must be in [0, V)")
+    d_freq = None
+    if weighted and freq is not None:
+        d_freq = on_dev(freq, torch.int32)
+        if int(d_freq.numel()) < S:
+            raise ValueError("freq holds %d sites, doc_off asks for %d" % (int(d_freq.numel()), S))
+        if S and (int(d_freq[:S].min()) < 0 or int(d_freq[:S].max()) > MAX_FREQ):
+            raise ValueError("frequencies must be in 0 .. 2^23 - 1")
+    mant = torch.empty((D,), dtype=torch.float64, device=dev)
+    expo, tok, bad = (torch.empty((D,), dtype=torch.int64, device=dev) for _ in range(3))
+    _native.heldout_loglik(d_off, d_word, d_freq, theta_dev, phi_t_dev, D, V, K,
+                           ld_theta=int(theta_dev.stride(0)) if D > 1 else K, ld_phi=int(phi_t_dev.stride(0)) if V > 1 else K,
+                           mant=mant, expo=expo, tok=tok, bad=bad)
+    return mant.cpu().numpy(), expo.cpu().numpy(), tok.cpu().numpy(), bad.cpu().numpy()
+
+
+_LN2 = math.log(2.0)
+
+
+def doc_logliks(mant, expo):
+    """ll_d = log(mant) + expo * ln 2, float64 [D]"""
+    return np.log(np.asarray(mant, dtype=np.float64)) + np.asarray(expo, dtype=np.int64).astype(np.float64) * _LN2
+
+
+def perplexity_from(mant, expo, tok, bad):
+    """dict(perplexity, loglik, tokens, bad) of the per-document outputs: the document log-likelihoods added one after the other
+    in document order (a plain float64 sum), perplexity = exp(-loglik / tokens); inf when a site of any document had no finite
+    positive probability, nan when nothing was scored."""
+    total = 0.0
+    for x in doc_logliks(mant, expo).tolist():
+        total += x
+    tokens, n_bad = int(np.asarray(tok, dtype=np.int64).sum()), int(np.asarray(bad, dtype=np.int64).sum())
+    if n_bad > 0:
+        ppl = float("inf")
+    elif tokens == 0:
+        ppl = float("nan")
+    else:
+        ppl = float(np.exp(-total / tokens))
+    return dict(perplexity=ppl, loglik=total, tokens=tokens, bad=n_bad)
