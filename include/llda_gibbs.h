@@ -114,18 +114,29 @@ typedef struct llda_sweep_args {
     int32_t  docs_per_group;     /* documents a lane group walks per workgroup (>=1; 0 = auto) */
     int32_t  dense_mask;         /* 1 = lab_mask allows every topic in every document (the kernel may
                                     then skip applying it); 0 = general                            */
-    int32_t  debug_margin;       /* 0 in production.  Test hook of the two-tier draw: n > 0 widens the
-                                    tier-1 safety margin to 2^-n of the total score (more sites take the
-                                    exact tier), -1 sends every site through the exact tier, -2 skips only
-                                    the fp32 tier 0; -3 (wide layouts only) production margins on the kernel
-                                    that keeps nothing of the row in registers, -4 on the register kernel with
-                                    LDS copies of the counts whatever max_doc_tokens says, -5 on the fp64 register
-                                    kernel without its fp32 tier, -6 the fp32 tier with fp64 factors in LDS even when
-                                    scratch is there, -7 with fp32 factors only whenever scratch is there; -8 (with n_kw16)
-                                    production margins on the three-wave form of the 16-bit-row kernel; -9 (with row16) the quad
-                                    kernel with the constant tier-0 margin 104 * 2^-24 of the total instead of its data-dependent one;
-                                    -10 ... -18 (with row16) the data-dependent margin scaled by 1 / 1.05 (the derived error bound itself),
-                                    1/2, 1/4 ... 1/256: tests/neartie.py measures how much of the margin the worst planted tie needs */
+    int32_t  debug_margin;       /* 0 in production.  Test hook of the tiered draw (dm below; csrc/sweep_plan.hpp is the one place
+                                    that reads it, tests/test_sweep_plan_host.py checks this table).  Results never depend on it.
+                                    Margins every kernel family starts from:
+                                      tier 1 (fp64)  2^-40 of the total score for dm == 0 and -8 <= dm <= -2; 2^-dm for dm > 0 (wider:
+                                                     more sites take the exact tier); off (every site exact) for dm == -1, dm <= -9
+                                      tier 0 (fp32)  production for dm in {0, -8}; 2^-dm for 1 <= dm <= 15; off otherwise
+                                    Sparse label sets (live_off / live_pos): any dm < 0 sends every site through the exact pipeline.
+                                    Wide layouts with a dense or general mask:
+                                      dm >= -1  the fp32-tiered kernel (tier 0: production margin at 0, 2^-dm for 1 .. 15, else off);
+                                                like -6 and -7 it needs 0 < max_doc_tokens < 32768, the register kernel runs otherwise
+                                      -2, -5    the fp64 register kernel without the fp32 tier
+                                      -3        the same decision on the kernel that keeps nothing of the row in registers
+                                      -4        the register kernel with LDS copies of the counts whatever max_doc_tokens says
+                                      -6        the fp32-tiered kernel with fp64 factors in LDS even when scratch is there
+                                      -7        the fp32-tiered kernel with fp32 factors only whenever scratch is there
+                                      <= -8     the fp64 register kernel (-8: production tier 1; below: every site exact)
+                                    With n_kw16 and site_row:  -8  production margins on the three-wave form of the 16-bit-row kernel.
+                                    With row16 (the quad kernel; tier 1 in production for -9 ... -18):
+                                      0           its data-dependent tier-0 margin
+                                      -9          the constant tier-0 margin 104 * 2^-24 of the total instead
+                                      -10 .. -18  the data-dependent margin scaled by 1 / 1.05 (the derived error bound itself), 1/2, 1/4 ...
+                                                  1/256: tests/neartie.py measures how much of it the worst planted tie needs
+                                      other dm    the margins every family starts from                                        */
     double   alpha, beta;        /* priors (LabeledLDA.py:55-56)                               */
     uint64_t seed;               /* RNG key                                                    */
     uint32_t sweep;              /* RNG counter word 3                                         */

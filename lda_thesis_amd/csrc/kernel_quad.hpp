@@ -25,8 +25,8 @@ namespace {
 // compared directly (98.2 v), chain B against the bounds minus chain A's total (99.2 v) -- inside the 105 v of the 2-document kernel,
 // margin 128 v.  Int32 rows with counts >= 2^24: + 2 v.
 // ---------------------------------------------------------------------------------------------
-constexpr float LLDA_MARGIN0_QUAD = 0x1.ap-18f;   // tier-0 margin of this kernel relative to the total: 104 * 2^-24 (bound 99.2 v, 101.2 v with
-                                                  // int32 counts >= 2^24) -- what the test hooks scale; production uses the sharper form below
+// LLDA_MARGIN0_QUAD (sweep_plan.hpp): the tier-0 margin of this kernel relative to the total, 104 * 2^-24 (bound 99.2 v, 101.2 v with
+// int32 counts >= 2^24) -- what the test hooks scale; production uses the sharper form below
 // The data-dependent margin (production).  With v = 2^-24 and true values L (lane total), P (the lanes before), t = u * total, the
 // compared difference  q~[s] - (tg~ -+ m)  is off by at most
 //     28.1 v L  (prefix: 12 v of the terms + 16 roundings)  + 1 v L (chain B against the bounds minus chain A's total)

@@ -701,9 +701,7 @@ __device__ __noinline__ int wide_rare_tiers(const WParams *Pk, double *scr, cons
     return zn;
 }
 
-#ifndef LLDA_MARGIN0_WIDE
-#define LLDA_MARGIN0_WIDE (112.0f * 0x1p-24f)
-#endif
+// (LLDA_MARGIN0_WIDE = 112 * 2^-24 has its default in sweep_plan.hpp: the host passes it as margin0_rel)
 
 // TC = slots per virtual lane / 4 (3 or 4: the only values wide layouts have).  (Registers: two rows, the prefix values and
 // the fp64 tier's temporaries want more than the 168 VGPRs of three wavefronts per SIMD -- with that cap the allocator

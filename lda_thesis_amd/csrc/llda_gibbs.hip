@@ -9,14 +9,19 @@
 //     LabeledLDA.py:117) is lane-local: one accumulator chain = one lane walking its slots, the 8 accumulators
 //     of a 128-topic leaf = 8 neighbouring lanes;
 //   * the n_kw row of the current word is one contiguous KP*4-byte read (word-major layout), prefetched one
-//     site ahead; count updates are int32 atomics into n_kw_delta and, through an LDS accumulator per workgroup,
-//     into n_k_delta.  Snapshot semantics + integer atomics => bit-deterministic;
+//     site ahead.  A changed site stores ONE word (old position | new position << 16) at its word-major place in the
+//     commit log, which llda_commit_log folds into n_kw word by word without global atomics (callers without a
+//     log: two int32 atomics into n_kw_delta per changed site); n_k_delta is updated through an LDS accumulator per
+//     workgroup.  Snapshot semantics + integer sums => bit-deterministic;
 //   * the draw is TIERED: an fp32 decision with a proven margin, an fp64 decision, and the
 //     reference's fp64 pipeline bit for bit (IEEE division, numpy-ordered sum, keyed Philox4x32-10 draw) for
 //     the sites the cheaper tiers cannot decide -- the chosen topic is always the exact pipeline's.
 // No MFMA (gather/scan, not a contraction).  FMA contraction is OFF: the reference rounds after every ufunc.
 //
 // Contents (one translation unit; the headers are included in this order)
+//   build_info.hpp      llda_build_info() from the preprocessor alone (host only)
+//   sweep_plan.hpp      sweep_plan            what llda_sweep launches -- family, template choices, margins, grid, LDS -- as a
+//                                             pure function of its arguments and the layout (host only; the debug_margin table)
 //   device_common.hpp   kernel parameters, Philox, row loads, one-hot updates, exact division, DPP / permlane
 //                       cross-lane moves, numpy-ordered group sum, keyed categorical draw (exact)
 //   draw_tiers.hpp      tier-0 (fp32) decision, cold tiers (fp64 decision, exact pipeline), commit of a site
@@ -40,9 +45,7 @@
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
-#ifndef ABL_EXTRA_LDS_BYTES
-#define ABL_EXTRA_LDS_BYTES 0      // occupancy ablation: dynamic LDS nobody uses (tools: -DABL_EXTRA_LDS_BYTES=20000 -> 2 workgroups per CU)
-#endif
+#include "sweep_plan.hpp"
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
@@ -76,6 +79,8 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+static_assert(SWEEP_MAX_LIVE == LLDA_MAX_LIVE && SWEEP_QUAD_THREADS == QNT, "sweep_plan.hpp restates two kernel constants");
+
 void add_leaves(llda_layout *L, int n, int start)
 {
     if (n <= 128) {
@@ -135,6 +140,38 @@ int hip_fail(hipError_t e)
     return LLDA_E_HIP;
 }
 
+// the return code of an entry point after its last launch
+int launched()
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+}
+
+// run-time value -> template argument: f(std::integral_constant<int, V>) for the V that v equals, LLDA_E_BAD_K when none does
+template <int... Vs, typename F>
+int visit_int(int v, F &&f)
+{
+    int rc = LLDA_E_BAD_K;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+
+template <typename F>
+int visit_bool(bool b, F &&f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// the narrow layouts llda_layout_init makes: 8 lanes with 1, 2, 4, 8, 12 or 16 slots, 16 / 32 / 64 lanes with 12 or 16
+template <typename F>
+int visit_layout(int G, int T, F &&f)
+{
+    return visit_int<8, 16, 32, 64>(G, [&](auto g) {
+        if constexpr (g.value == 8) return visit_int<1, 2, 4, 8, 12, 16>(T, [&](auto t) { return f(g, t); });
+        else return visit_int<12, 16>(T, [&](auto t) { return f(g, t); });
+    });
+}
+
 // The layout of K (128 KB of tables): built once per host thread and K, not once per call.
 const llda_layout *layout_of(int32_t K, int *rc)
 {
@@ -171,67 +208,96 @@ void fill_wide(const llda_layout &L, WideLayout &W)
     }
 }
 
-// one wavefront per document (or site): enough workgroups to fill the chip a few times over
-unsigned wide_blocks(int64_t n)
+// a kernel of llda_sweep on the grid, the block and the dynamic LDS of the plan
+template <typename Kern, typename... Args>
+int launch(Kern kern, const SweepPlan &p, hipStream_t st, const Args &...args)
 {
-    const int64_t cap = 256 * 16;
-    return (unsigned)(n < 1 ? 1 : (n < cap ? n : cap));
+    const int rl = allow_lds(kern, p.lds);
+    if (rl) return rl;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, st, args...);
+    return launched();
 }
 
+// SWEEP_EXACT, SWEEP_TIERED, SWEEP_ROWS16
 template <int G, int T>
-int launch_sweep(const KParams &P, bool has_tail, bool fast, bool dense, int64_t blocks, hipStream_t st)
+int launch_sweep(const KParams &P, const SweepPlan &p, hipStream_t st)
 {
-    const dim3 grid((unsigned)blocks), block(256);
     if constexpr (G <= 16) {
-        if (fast && P.commit_log && P.site_rec) {       // 16-byte site records (llda_sweep_args.site_rec)
-            if (dense) hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, true, true, true>), grid, block, 0, st, P);
-            else if (has_tail) hipLaunchKernelGGL((llda_sweep_kernel<G, T, true, false, true, true>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, false, true, true>), grid, block, 0, st, P);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        if (p.rec) {                                    // 16-byte site records (llda_sweep_args.site_rec)
+            if (p.dense) return launch(llda_sweep_kernel<G, T, false, true, true, true>, p, st, P);
+            if (p.has_tail) return launch(llda_sweep_kernel<G, T, true, false, true, true>, p, st, P);
+            return launch(llda_sweep_kernel<G, T, false, false, true, true>, p, st, P);
         }
     }
     if constexpr (G >= 32 && T == 16) {
-        if (P.n_kw16) {                                 // (llda_sweep checked: fast, dense, commit log)
-            if (P.w4) hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, true, true, false, true, true>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, true, true, false, true>), grid, block, ABL_EXTRA_LDS_BYTES, st, P);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        if (p.family == SWEEP_ROWS16) {
+            if (p.w4) return launch(llda_sweep_kernel<G, T, false, true, true, false, true, true>, p, st, P);
+            return launch(llda_sweep_kernel<G, T, false, true, true, false, true>, p, st, P);
         }
     }
-    if (!fast) {
-        if (has_tail) hipLaunchKernelGGL((llda_sweep_exact_kernel<G, T, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((llda_sweep_exact_kernel<G, T, false>), grid, block, 0, st, P);
-    } else if (dense) {
-        if (P.commit_log) hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, true, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, true, false>), grid, block, 0, st, P);
-    } else if (has_tail) {
-        if (P.commit_log) hipLaunchKernelGGL((llda_sweep_kernel<G, T, true, false, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((llda_sweep_kernel<G, T, true, false, false>), grid, block, 0, st, P);
-    } else {
-        if (P.commit_log) hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, false, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((llda_sweep_kernel<G, T, false, false, false>), grid, block, 0, st, P);
+    if (p.family == SWEEP_EXACT) {
+        if (p.has_tail) return launch(llda_sweep_exact_kernel<G, T, true>, p, st, P);
+        return launch(llda_sweep_exact_kernel<G, T, false>, p, st, P);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    if (p.dense) {
+        if (p.logged) return launch(llda_sweep_kernel<G, T, false, true, true>, p, st, P);
+        return launch(llda_sweep_kernel<G, T, false, true, false>, p, st, P);
+    }
+    if (p.has_tail) {
+        if (p.logged) return launch(llda_sweep_kernel<G, T, true, false, true>, p, st, P);
+        return launch(llda_sweep_kernel<G, T, true, false, false>, p, st, P);
+    }
+    if (p.logged) return launch(llda_sweep_kernel<G, T, false, false, true>, p, st, P);
+    return launch(llda_sweep_kernel<G, T, false, false, false>, p, st, P);
 }
 
-template <int G>
-int dispatch_sweep_T(int T, const KParams &P, bool has_tail, bool fast, bool dense, int64_t blocks, hipStream_t st)
+// SWEEP_SPARSE (Params = KParams) and SWEEP_WIDE_SPARSE (WSParams)
+template <typename Params>
+int launch_sparse(const llda_sweep_args *a, const SweepPlan &p, Params &P, hipStream_t st)
 {
-    if constexpr (G == 8) {
-        switch (T) {
-        case 1: return launch_sweep<8, 1>(P, has_tail, fast, dense, blocks, st);
-        case 2: return launch_sweep<8, 2>(P, has_tail, fast, dense, blocks, st);
-        case 4: return launch_sweep<8, 4>(P, has_tail, fast, dense, blocks, st);
-        case 8: return launch_sweep<8, 8>(P, has_tail, fast, dense, blocks, st);
-        }
+    P.live_off = a->live_off; P.live_pos = a->live_pos;
+    if (p.img) { P.img = a->n_kw_img; P.img_col = a->img_col; }
+    return visit_int<8, 16, 32, 64>(p.gs, [&](auto gs) {
+        return visit_int<0, 8, 16>(p.img, [&](auto img) {
+            return launch(llda_sweep_sparse_kernel<gs.value, Params, img.value>, p, st, P);
+        });
+    });
+}
+
+// SWEEP_WIDE_F32, SWEEP_WIDE_REG, SWEEP_WIDE_LDS
+int launch_wide(const llda_sweep_args *a, const SweepPlan &p, const WParams &W, hipStream_t st)
+{
+    if (p.family == SWEEP_WIDE_F32) {
+        double *scr = p.slim ? static_cast<double *>(a->scratch) : nullptr;
+        return visit_int<2, 3, 4, 5, 6, 7, 8>(p.nt, [&](auto nt) {
+            return visit_int<3, 4>(p.tc, [&](auto tc) {
+                return visit_bool(p.slim, [&](auto slim) {
+                    if constexpr (wide_f32_pair(nt.value, tc.value))
+                        return launch(llda_sweep_wide_f32_kernel<nt.value, tc.value, slim.value>, p, st, W, p.m0, scr);
+                    else return (int)LLDA_E_BAD_K;
+                });
+            });
+        });
     }
-    switch (T) {
-    case 12: return launch_sweep<G, 12>(P, has_tail, fast, dense, blocks, st);
-    case 16: return launch_sweep<G, 16>(P, has_tail, fast, dense, blocks, st);
-    }
-    return LLDA_E_BAD_K;
+    if (p.family == SWEEP_WIDE_REG)
+        return visit_int<2, 3, 4, 5, 6, 7, 8>(p.nt, [&](auto nt) {
+            return visit_bool(p.compact, [&](auto compact) {
+                return launch(llda_sweep_wide_reg_kernel<nt.value, compact.value>, p, st, W);
+            });
+        });
+    return visit_bool(p.tiered, [&](auto tiered) { return launch(llda_sweep_wide_kernel<tiered.value>, p, st, W); });
+}
+
+// SWEEP_QUAD
+int launch_quad(const SweepPlan &p, const KParams &P, hipStream_t st)
+{
+    return visit_int<2, 3, 4>(p.lb, [&](auto lb) {
+        return visit_bool(p.pad, [&](auto pad) {
+            return visit_bool(p.hooks, [&](auto hooks) {
+                return launch(llda_sweep_quad_kernel<lb.value, (lb.value < 4), pad.value, hooks.value>, p, st, P);
+            });
+        });
+    });
 }
 
 template <int G, int T>
@@ -239,26 +305,7 @@ int launch_loglik(const LParams &P, hipStream_t st)
 {
     const int64_t blocks = (P.D + (256 / G) - 1) / (256 / G);
     hipLaunchKernelGGL((llda_loglik_kernel<G, T>), dim3((unsigned)blocks), dim3(256), 0, st, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
-}
-
-template <int G>
-int dispatch_loglik_T(int T, const LParams &P, hipStream_t st)
-{
-    if constexpr (G == 8) {
-        switch (T) {
-        case 1: return launch_loglik<8, 1>(P, st);
-        case 2: return launch_loglik<8, 2>(P, st);
-        case 4: return launch_loglik<8, 4>(P, st);
-        case 8: return launch_loglik<8, 8>(P, st);
-        }
-    }
-    switch (T) {
-    case 12: return launch_loglik<G, 12>(P, st);
-    case 16: return launch_loglik<G, 16>(P, st);
-    }
-    return LLDA_E_BAD_K;
+    return launched();
 }
 
 template <int G, int T>
@@ -273,26 +320,7 @@ int launch_foldin(const FParams &P, bool has_tail, hipStream_t st)
     const int64_t blocks = (P.D + (256 / G) - 1) / (256 / G);
     if (has_tail) hipLaunchKernelGGL((llda_foldin_kernel<G, T, true>), dim3((unsigned)blocks), dim3(256), 0, st, P);
     else hipLaunchKernelGGL((llda_foldin_kernel<G, T, false>), dim3((unsigned)blocks), dim3(256), 0, st, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
-}
-
-template <int G>
-int dispatch_foldin_T(int T, const FParams &P, bool has_tail, hipStream_t st)
-{
-    if constexpr (G == 8) {
-        switch (T) {
-        case 1: return launch_foldin<8, 1>(P, has_tail, st);
-        case 2: return launch_foldin<8, 2>(P, has_tail, st);
-        case 4: return launch_foldin<8, 4>(P, has_tail, st);
-        case 8: return launch_foldin<8, 8>(P, has_tail, st);
-        }
-    }
-    switch (T) {
-    case 12: return launch_foldin<G, 12>(P, has_tail, st);
-    case 16: return launch_foldin<G, 16>(P, has_tail, st);
-    }
-    return LLDA_E_BAD_K;
+    return launched();
 }
 
 template <int G, int T>
@@ -301,26 +329,7 @@ int launch_theta(const RParams &P, bool has_tail, hipStream_t st)
     const int64_t blocks = (P.D + (256 / G) - 1) / (256 / G);
     if (has_tail) hipLaunchKernelGGL((llda_readout_theta_kernel<G, T, true>), dim3((unsigned)blocks), dim3(256), 0, st, P);
     else hipLaunchKernelGGL((llda_readout_theta_kernel<G, T, false>), dim3((unsigned)blocks), dim3(256), 0, st, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
-}
-
-template <int G>
-int dispatch_theta_T(int T, const RParams &P, bool has_tail, hipStream_t st)
-{
-    if constexpr (G == 8) {
-        switch (T) {
-        case 1: return launch_theta<8, 1>(P, has_tail, st);
-        case 2: return launch_theta<8, 2>(P, has_tail, st);
-        case 4: return launch_theta<8, 4>(P, has_tail, st);
-        case 8: return launch_theta<8, 8>(P, has_tail, st);
-        }
-    }
-    switch (T) {
-    case 12: return launch_theta<G, 12>(P, has_tail, st);
-    case 16: return launch_theta<G, 16>(P, has_tail, st);
-    }
-    return LLDA_E_BAD_K;
+    return launched();
 }
 
 // the summation schedule shared by llda_sweep and llda_foldin
@@ -440,18 +449,6 @@ int64_t llda_sweep_scratch_bytes(int32_t K, int64_t D)
     return (int64_t)wide_blocks(D) * Lp->KP * 8;          // one row of doubles per workgroup of the wide sweep
 }
 
-// llda_sweep_args.n_kw_img / img_bits -> KParams.img of a sparse-label launch
-static int take_image(const llda_sweep_args *a, KParams &P)
-{
-    P.img = nullptr;
-    if (!a->n_kw_img && !a->img_bits) return LLDA_OK;
-    if (!a->n_kw_img || (a->img_bits != 8 && a->img_bits != 16)) return LLDA_E_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(a->n_kw_img) & (a->img_bits == 8 ? 3 : 7)) return LLDA_E_BAD_ARG;     // (as llda_pack_image)
-    P.img = a->n_kw_img;
-    P.img_col = a->img_col;
-    return LLDA_OK;
-}
-
 int llda_sweep(const llda_sweep_args *a, void *stream)
 {
     if (!a || a->D < 0 || a->V < 1) return LLDA_E_BAD_ARG;
@@ -459,13 +456,9 @@ int llda_sweep(const llda_sweep_args *a, void *stream)
     const llda_layout *Lp = layout_of(a->K, &rc);
     if (rc) return rc;
     const llda_layout &L = *Lp;
-    if (a->D == 0) return LLDA_OK;            // an empty shard: nothing to do, array pointers may be NULL
-    if (a->n_sites < 0 || a->n_sites >= (1LL << 30)) return LLDA_E_BAD_ARG;   // split the shard (llda_gibbs.h)
-    const bool logged = a->csc_pos && a->commit_log;
-    if ((a->csc_pos != nullptr) != (a->commit_log != nullptr)) return LLDA_E_BAD_ARG;
-    if (!a->doc_off || !a->word || !a->freq || !a->z || !a->lab_mask || !a->n_dk || !a->n_kw ||
-        (!a->n_kw_delta && !logged) || !a->n_k || !a->n_k_delta)
-        return LLDA_E_BAD_ARG;
+    SweepPlan p;
+    rc = sweep_plan(*a, L, QUAD_HOOKS_OUT, &p);
+    if (rc || p.family == SWEEP_NONE) return rc;
 
     KParams P;
     memset(&P, 0, sizeof P);
@@ -473,7 +466,7 @@ int llda_sweep(const llda_sweep_args *a, void *stream)
     P.lab_mask = a->lab_mask; P.n_dk = a->n_dk; P.n_kw = a->n_kw; P.n_kw_delta = a->n_kw_delta;
     P.n_k = a->n_k; P.n_k_delta = a->n_k_delta; P.status = a->status;
     P.csc_pos = a->csc_pos; P.commit_log = a->commit_log;
-    P.site_rec = logged ? a->site_rec : nullptr;
+    P.site_rec = p.site_rec ? a->site_rec : nullptr;
     P.D = a->D; P.doc_base = a->doc_base;
     P.alpha = a->alpha; P.beta = a->beta;
     P.vbeta = (double)a->V * a->beta;                       // V * beta evaluated first (LabeledLDA.py:115)
@@ -482,244 +475,45 @@ int llda_sweep(const llda_sweep_args *a, void *stream)
     P.sweep = a->sweep; P.stream_id = a->stream_id;
     fill_schedule(L, P.last_leaf, P.tail, P.tail_row, P.n_rounds, P.xor_tree, P.rounds_pk);
     P.KP = L.KP;
-    if (P.site_rec && L.G <= 16 && a->n_sites >= (1LL << 28)) return LLDA_E_BAD_ARG;   // 16-byte records: 32-bit offsets
-    const bool has_tail = L.tail != 0;
-    // with alpha, beta >= 1e-6 and int32 counts no label-allowed score can underflow to zero ...
-    // ... and with V*beta < 2^40 the fp32 / fp64 reciprocals of n_k + V*beta stay in range
-    const bool fast = a->alpha >= 1e-6 && a->beta >= 1e-6 && P.vbeta < 1099511627776.0;
-    // all-ones label masks and no padded slots: the mask need not be applied at all
-    const bool dense = fast && a->dense_mask != 0 && L.K == L.KP;
-    // debug_margin: 0 = production margins; n > 0 = 2^-n (wider: more fallbacks); -1 = always exact tier;
-    // -2 = no fp32 tier
-    P.margin_rel = a->debug_margin == 0 || a->debug_margin == -2 || a->debug_margin == -3 || a->debug_margin == -4 || a->debug_margin == -5 || a->debug_margin == -6 || a->debug_margin == -7 || a->debug_margin == -8 ? 0x1p-40 : (a->debug_margin > 0 ? ldexp(1.0, -a->debug_margin) : 2.0);
-    P.margin0_rel = a->debug_margin == 0 || a->debug_margin == -8 ? (float)LLDA_MARGIN0 : (a->debug_margin > 0 && a->debug_margin < 16 ? ldexpf(1.0f, -a->debug_margin) : 2.0f);
+    P.margin_rel = p.margin_rel; P.margin0_rel = p.margin0_rel; P.margin0_data = p.margin0_data;
+    P.dpg = p.dpg;
     hipStream_t st = (hipStream_t)stream;
 
-    if (L.wide && fast && a->dense_mask == 0 && a->live_off && a->live_pos && a->live_max >= 1 &&
-        a->live_max <= LLDA_MAX_LIVE) {
-        // sparse label sets on a wide layout: one lane per allowed topic, the wide exact tier for undecided sites
+    switch (p.family) {
+    case SWEEP_SPARSE:
+        return launch_sparse(a, p, P, st);
+    case SWEEP_WIDE_SPARSE: {
         WSParams W;
         memset(&W, 0, sizeof W);
         static_cast<KParams &>(W) = P;
-        W.site_rec = nullptr;
-        W.live_off = a->live_off; W.live_pos = a->live_pos;
-        if (a->debug_margin < 0) {                          // test hook: every site goes through the exact pipeline
-            W.margin_rel = 2.0;
-            W.margin0_rel = 2.0f;                           // (also with -8, which keeps the fp32 tier only for the dense 16-bit-row kernel)
-        }
         fill_wide(L, W.w);
-        const int GS = a->live_max <= 8 ? 8 : a->live_max <= 16 ? 16 : a->live_max <= 32 ? 32 : 64;
-        int dpg = a->docs_per_group < 1 ? 1 : a->docs_per_group;
-        W.dpg = dpg;
-        const int64_t per_block = (int64_t)(256 / GS) * dpg;
-        const int64_t blocks = (a->D + per_block - 1) / per_block;
-        if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
-        const size_t lds = (size_t)L.KP * 8 + 16;
-        const dim3 grid((unsigned)blocks), block(256);
-        int rl;
-        const int rimg = take_image(a, W);
-        if (rimg) return rimg;
-#define LLDA_SPARSE_WIDE_I(GS_, IMG_)                                                                       \
-        rl = allow_lds(llda_sweep_sparse_kernel<GS_, WSParams, IMG_>, lds);                                 \
-        if (rl) return rl;                                                                                  \
-        hipLaunchKernelGGL((llda_sweep_sparse_kernel<GS_, WSParams, IMG_>), grid, block, lds, st, W);
-#define LLDA_SPARSE_WIDE(GS_)                                                                       \
-    case GS_:                                                                                       \
-        if (a->img_bits == 8) { LLDA_SPARSE_WIDE_I(GS_, 8) }                                        \
-        else if (a->img_bits == 16) { LLDA_SPARSE_WIDE_I(GS_, 16) }                                 \
-        else { LLDA_SPARSE_WIDE_I(GS_, 0) }                                                         \
-        break;
-        switch (GS) { LLDA_SPARSE_WIDE(8) LLDA_SPARSE_WIDE(16) LLDA_SPARSE_WIDE(32) LLDA_SPARSE_WIDE(64) }
-#undef LLDA_SPARSE_WIDE
-#undef LLDA_SPARSE_WIDE_I
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        return launch_sparse(a, p, W, st);
     }
-    if (L.wide) {                                           // more than 8 pairwise leaves: the general path
-        if (a->n_kw_img || a->img_bits) return LLDA_E_BAD_ARG;   // the narrow image belongs to the sparse-label kernels
+    case SWEEP_WIDE_F32:
+    case SWEEP_WIDE_REG:
+    case SWEEP_WIDE_LDS: {
         WParams W;
         memset(&W, 0, sizeof W);
         W.k = P;
-        W.k.site_rec = nullptr;
         fill_wide(L, W.w);
-        const size_t lds = (size_t)L.KP * 16;               // scores (f64) + n_dk + n_k (int32), per wavefront
-        const dim3 grid(wide_blocks(a->D)), block(64);
-        int rl = LLDA_OK;
-#define LLDA_WIDE_REG(NT_, C_)                                                                               \
-    case NT_:                                                                                                \
-        rl = allow_lds(llda_sweep_wide_reg_kernel<NT_, C_>, lds_reg);                                        \
-        if (rl) return rl;                                                                                   \
-        hipLaunchKernelGGL((llda_sweep_wide_reg_kernel<NT_, C_>), grid, block, lds_reg, st, W);              \
-        break;
-        // counts as start values + int16 changes (no document may then hold 2^15 tokens): 10 instead of 16 bytes of LDS
-        // per position
-        const bool compact = a->max_doc_tokens > 0 && a->max_doc_tokens < 32768 && a->debug_margin != -4;
-        const size_t lds_reg = compact ? (size_t)L.KP * 10 : lds;
-        // fp32 tier 0 in front of the fp64 decision (needs the int16 count changes): production
-        const bool tier0 = fast && compact && a->debug_margin != -2 && a->debug_margin != -3 && a->debug_margin != -5 &&
-                           (a->debug_margin >= -1 || a->debug_margin == -6 || a->debug_margin == -7);
-        if (tier0) {
-            // margins: production, or the test hook's (n > 0: 2^-n for tier 0 below 16, else tier 0 off; -1: everything exact)
-            const float m0 = a->debug_margin == 0 || a->debug_margin == -6 || a->debug_margin == -7 ? LLDA_MARGIN0_WIDE
-                             : (a->debug_margin > 0 && a->debug_margin < 16 ? ldexpf(1.0f, -a->debug_margin) : 2.0f);
-            // fp32 factors only in LDS (6 bytes per position) when the caller brought the scratch rows of the rare tiers
-            // (measured faster only for three and four tiers: see the note at the kernel; -7 forces it for tests and ablations)
-            const bool slim = a->scratch && a->scratch_bytes >= llda_sweep_scratch_bytes(a->K, a->D) && a->debug_margin != -6 &&
-                              (a->debug_margin == -7 || L.tiers == 3 || L.tiers == 4);
-            const size_t lds32 = slim ? (size_t)L.KP * 6 : lds_reg;
-            double *scr = slim ? static_cast<double *>(a->scratch) : nullptr;
-#define LLDA_WIDE_F32(NT_, TC_)                                                                              \
-    if (L.tiers == NT_ && L.T == 4 * TC_) {                                                                  \
-        if (slim) {                                                                                          \
-            rl = allow_lds(llda_sweep_wide_f32_kernel<NT_, TC_, true>, lds32);                               \
-            if (rl) return rl;                                                                               \
-            hipLaunchKernelGGL((llda_sweep_wide_f32_kernel<NT_, TC_, true>), grid, block, lds32, st, W, m0, scr);  \
-        } else {                                                                                             \
-            rl = allow_lds(llda_sweep_wide_f32_kernel<NT_, TC_, false>, lds32);                              \
-            if (rl) return rl;                                                                               \
-            hipLaunchKernelGGL((llda_sweep_wide_f32_kernel<NT_, TC_, false>), grid, block, lds32, st, W, m0, scr); \
-        }                                                                                                    \
-    } else
-            LLDA_WIDE_F32(2, 3) LLDA_WIDE_F32(2, 4) LLDA_WIDE_F32(3, 4) LLDA_WIDE_F32(4, 3) LLDA_WIDE_F32(4, 4) LLDA_WIDE_F32(5, 4)
-            LLDA_WIDE_F32(6, 4) LLDA_WIDE_F32(7, 4) LLDA_WIDE_F32(8, 3) LLDA_WIDE_F32(8, 4)
-                return LLDA_E_BAD_K;
-#undef LLDA_WIDE_F32
-        } else if (fast && a->debug_margin != -3 && compact) {     // the tiered kernel with the row in registers
-            switch (L.tiers) {
-                LLDA_WIDE_REG(2, true) LLDA_WIDE_REG(3, true) LLDA_WIDE_REG(4, true) LLDA_WIDE_REG(5, true)
-                LLDA_WIDE_REG(6, true) LLDA_WIDE_REG(7, true) LLDA_WIDE_REG(8, true)
-            default: return LLDA_E_BAD_K;
-            }
-        } else if (fast && a->debug_margin != -3) {
-            switch (L.tiers) {
-                LLDA_WIDE_REG(2, false) LLDA_WIDE_REG(3, false) LLDA_WIDE_REG(4, false) LLDA_WIDE_REG(5, false)
-                LLDA_WIDE_REG(6, false) LLDA_WIDE_REG(7, false) LLDA_WIDE_REG(8, false)
-            default: return LLDA_E_BAD_K;
-            }
-        } else if (fast) {                                  // (debug_margin -3: the same decision on the LDS-only kernel)
-            rl = allow_lds(llda_sweep_wide_kernel<true>, lds);
-            if (rl) return rl;
-            hipLaunchKernelGGL(llda_sweep_wide_kernel<true>, grid, block, lds, st, W);
-        } else {                                            // tiny priors: every site through the exact pipeline
-            rl = allow_lds(llda_sweep_wide_kernel<false>, lds);
-            if (rl) return rl;
-            hipLaunchKernelGGL(llda_sweep_wide_kernel<false>, grid, block, lds, st, W);
-        }
-#undef LLDA_WIDE_REG
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        return launch_wide(a, p, W, st);
     }
-
-    // sparse label sets: one lane per allowed topic (a site the margin cannot decide is resolved inside the kernel by
-    // the exact pipeline, exact_site_wave)
-    const bool sparse = fast && !dense && a->live_off && a->live_pos && a->live_max >= 1 && a->live_max <= LLDA_MAX_LIVE;
-    const int G = sparse ? (a->live_max <= 8 ? 8 : a->live_max <= 16 ? 16 : a->live_max <= 32 ? 32 : 64) : L.G;
-    const int gpb = 256 / G;
-    int dpg = a->docs_per_group;
-    // auto: one pass of documents per workgroup.  Workgroups of equal-length documents finish in lock step, so
-    // the tail of the launch idles for up to one workgroup's run time: the shorter the workgroup the better
-    // (synth2: 3540 M sites/s at 1, 3341 at 4, 3205 at 6 documents per lane group)
-    if (dpg < 1) dpg = 1;
-    P.dpg = dpg;
-    const int64_t per_block = (int64_t)gpb * dpg;
-    const int64_t blocks = (a->D + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
-
-    if (sparse) {
-        P.live_off = a->live_off; P.live_pos = a->live_pos;
-        if (a->debug_margin < 0) {                         // test hook: every site goes through the exact pipeline
-            P.margin_rel = 2.0;
-            P.margin0_rel = 2.0f;                          // (also with -8, which keeps the fp32 tier only for the dense 16-bit-row kernel)
-        }
-        const dim3 grid((unsigned)blocks), block(256);
-        const int rimg = take_image(a, P);
-        if (rimg) return rimg;
-#define LLDA_SPARSE(GS_)                                                                                              \
-    case GS_:                                                                                                         \
-        if (a->img_bits == 8) hipLaunchKernelGGL((llda_sweep_sparse_kernel<GS_, KParams, 8>), grid, block, 0, st, P);       \
-        else if (a->img_bits == 16) hipLaunchKernelGGL((llda_sweep_sparse_kernel<GS_, KParams, 16>), grid, block, 0, st, P); \
-        else hipLaunchKernelGGL((llda_sweep_sparse_kernel<GS_, KParams, 0>), grid, block, 0, st, P);                       \
-        break;
-        switch (G) { LLDA_SPARSE(8) LLDA_SPARSE(16) LLDA_SPARSE(32) LLDA_SPARSE(64) }
-#undef LLDA_SPARSE
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
-    }
-    if (a->n_kw_img || a->img_bits) return LLDA_E_BAD_ARG;         // the narrow image belongs to the sparse-label kernels
-    if (a->row16) {
-        // four / eight / sixteen documents per wavefront (kernel_quad.hpp): K = 512 / 256 / 128 dense with the commit log, every row in
-        // the 16-bit image, flags per word from llda_pack_rows16_all, documents below 2^16 tokens
-        if (!a->n_kw16 || a->site_row) return LLDA_E_BAD_ARG;
-        if (!(fast && a->dense_mask != 0 && logged && llda_quad_ok(a->K))) return LLDA_E_BAD_ARG;
-        if (a->D >= (1LL << 31)) return LLDA_E_BAD_ARG;
-        P.quad_pad = L.K != L.KP;
-        if (P.quad_pad && !P.lab_mask) return LLDA_E_BAD_ARG;
-        if (!(a->max_doc_tokens > 0 && a->max_doc_tokens < 65536)) return LLDA_E_BAD_ARG;
-        if ((reinterpret_cast<uintptr_t>(a->n_kw16) | reinterpret_cast<uintptr_t>(a->n_kw)) & 15) return LLDA_E_BAD_ARG;
-        if (a->V >= (1LL << 22)) return LLDA_E_BAD_ARG;                  // (the image is addressed with 32-bit byte offsets)
-        // (the commit log too: log position << 2 in 32 bits.  The general check above refuses such a call for the site arrays' sake;
-        // this kernel's own reason stands here, with its other bounds, so that it survives a change of that one)
-        if (a->n_sites >= (1LL << 30)) return LLDA_E_BAD_ARG;
-        if (L.G <= 16 && !P.site_rec) return LLDA_E_BAD_ARG;             // (8 / 16 documents per wavefront read 16-byte site records)
-        if (a->n_sites < 1) return LLDA_OK;                              // (documents without sites: nothing to sample)
+    case SWEEP_QUAD:
         P.n_kw16 = a->n_kw16;
         P.row16 = a->row16;
-        if (a->debug_margin == 0) {                                       // (this kernel's own, data-dependent bound: kernel_quad.hpp)
-            P.margin0_rel = 0.0f;
-            P.margin0_data = 1.0f;
-        } else if (a->debug_margin == -9) {                               // test hook: the constant margin 104 * 2^-24 of the total
-            P.margin0_rel = LLDA_MARGIN0_QUAD;
-            P.margin_rel = 0x1p-40;
-        } else if (a->debug_margin <= -10 && a->debug_margin >= -18) {    // test hooks: the data-dependent margin SCALED DOWN -- by 1 / 1.05
-            P.margin0_rel = 0.0f;                                         // (the derived bound itself), 1/2, 1/4 ... 1/256: how much of the
-            P.margin0_data = a->debug_margin == -10 ? 1.0f / 1.05f : ldexpf(1.0f, a->debug_margin + 10);   // margin the worst site needs
-            P.margin_rel = 0x1p-40;
-        }
-        const int64_t per_q = (int64_t)(2 * QNT / L.G) * dpg;             // (a document is G / 2 lanes)
-        const int64_t qblocks = (a->D + per_q - 1) / per_q;
-        if (qblocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
-        // (K = 512 with the site records measured SLOWER: 5.19 vs 4.84 ms on 125 000 documents -- four documents per wavefront are not
-        // bound by the address pipeline, and the records are 4 more bytes per site)
-        const dim3 qgrid((unsigned)qblocks), qblock(QNT);
-        // every debug_margin != 0 runs the instantiation that reads the margins of both tiers from the arguments (HOOKS); production has
-        // them compiled in
-        const bool hooks = a->debug_margin != 0 || !QUAD_HOOKS_OUT;
-#define LLDA_QUAD(LB_, REC_, PAD_)                                                                                                    \
-        do {                                                                                                                           \
-            if (hooks) hipLaunchKernelGGL((llda_sweep_quad_kernel<LB_, REC_, PAD_, true>), qgrid, qblock, 0, st, P);                   \
-            else hipLaunchKernelGGL((llda_sweep_quad_kernel<LB_, REC_, PAD_, false>), qgrid, qblock, 0, st, P);                        \
-        } while (0)
-        if (!P.quad_pad) {
-            if (L.G == 32) LLDA_QUAD(4, false, false);
-            else if (L.G == 16) LLDA_QUAD(3, true, false);
-            else LLDA_QUAD(2, true, false);
-        } else {                                                          // K < KP: positions without a topic
-            if (L.G == 32) LLDA_QUAD(4, false, true);
-            else if (L.G == 16) LLDA_QUAD(3, true, true);
-            else LLDA_QUAD(2, true, true);
-        }
-#undef LLDA_QUAD
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
-    }
-    if ((a->n_kw16 != nullptr) != (a->site_row != nullptr)) return LLDA_E_BAD_ARG;
-    if (a->n_kw16) {
-        // 16-bit rows (bit 31 of csc_pos): the dense 16-slot kernel with the commit log, nothing else knows the flag
-        if (!(fast && dense && logged && L.T == 16 && L.G >= 32)) return LLDA_E_BAD_ARG;
-        if ((reinterpret_cast<uintptr_t>(a->n_kw16) | reinterpret_cast<uintptr_t>(a->n_kw)) & 15) return LLDA_E_BAD_ARG;
+        P.quad_pad = p.pad;
+        return launch_quad(p, P, st);
+    case SWEEP_ROWS16:
         P.n_kw16 = a->n_kw16;
         P.site_row = a->site_row;
-        // four waves per SIMD: n_dk and its sweep-start value share an LDS word (debug_margin -8: the three-wave form regardless)
-        P.w4 = a->max_doc_tokens > 0 && a->max_doc_tokens < 65536 && a->debug_margin != -8;
+        P.w4 = p.w4;
+        break;
+    default:
+        break;
     }
-    switch (L.G) {
-    case 8: return dispatch_sweep_T<8>(L.T, P, has_tail, fast, dense, blocks, st);
-    case 16: return dispatch_sweep_T<16>(L.T, P, has_tail, fast, dense, blocks, st);
-    case 32: return dispatch_sweep_T<32>(L.T, P, has_tail, fast, dense, blocks, st);
-    case 64: return dispatch_sweep_T<64>(L.T, P, has_tail, fast, dense, blocks, st);
-    }
-    return LLDA_E_BAD_K;
+    return visit_layout(L.G, L.T, [&](auto g, auto t) { return launch_sweep<g.value, t.value>(P, p, st); });
 }
+
 
 int llda_sweep_batch(const llda_batch_args *a, void *stream)
 {
@@ -740,7 +534,7 @@ int llda_sweep_batch(const llda_batch_args *a, void *stream)
     P.alpha = a->alpha; P.beta = a->beta; P.vbeta = (double)a->V * a->beta;
     // the sparse arithmetic needs strictly positive scores and an in-range reciprocal (as llda_sweep's tiered kernels)
     if (!(a->alpha >= 1e-6 && a->beta >= 1e-6 && P.vbeta < 1099511627776.0)) return LLDA_E_BAD_ARG;
-    P.margin_rel = a->debug_margin == 0 ? 0x1p-40 : (a->debug_margin > 0 ? ldexp(1.0, -a->debug_margin) : 2.0);
+    P.margin_rel = batch_margin_rel(a->debug_margin);
     P.key0 = (uint32_t)a->seed; P.key1 = (uint32_t)(a->seed >> 32); P.sweep = a->sweep;
     const int gpb = 256 / a->lanes;
     const int64_t blocks = (a->n_inst + gpb - 1) / gpb;
@@ -753,8 +547,7 @@ int llda_sweep_batch(const llda_batch_args *a, void *stream)
     case 32: hipLaunchKernelGGL(llda_sweep_batch_kernel<32>, grid, block, 0, st, P); break;
     default: hipLaunchKernelGGL(llda_sweep_batch_kernel<64>, grid, block, 0, st, P); break;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_commit_log(const int64_t *item_begin, const int32_t *item_len, const int32_t *item_word, int64_t n_items,
@@ -778,8 +571,7 @@ int llda_commit_log(const int64_t *item_begin, const int32_t *item_len, const in
     const int rl = allow_lds(llda_commit_log_kernel, 4 * L.KP * sizeof(int));      // (above 64 KB from KP = 4 096 on)
     if (rl) return rl;
     hipLaunchKernelGGL(llda_commit_log_kernel, dim3((unsigned)blocks), dim3(256), 4 * L.KP * sizeof(int), (hipStream_t)stream, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_apply_rows(const int64_t *row_off, int32_t *rows, int64_t n_rows, int32_t K, int32_t *counts, void *stream)
@@ -795,8 +587,7 @@ int llda_apply_rows(const int64_t *row_off, int32_t *rows, int64_t n_rows, int32
     if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
     hipLaunchKernelGGL(llda_apply_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, row_off, rows,
                        n_rows, L.KP, counts);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_rows16_ok(int32_t K)
@@ -828,8 +619,7 @@ int llda_pack_rows16(const int32_t *n_kw, const uint8_t *row16, int64_t V, int32
     if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
     hipLaunchKernelGGL(llda_pack_rows16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_kw, row16, n_kw16,
                        V, L.G, status);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_pack_image_cols(const int32_t *n_kw, int64_t V, int32_t K, int32_t bits, const int32_t *col_src, void *img, void *stream)
@@ -840,15 +630,14 @@ int llda_pack_image_cols(const int32_t *n_kw, int64_t V, int32_t K, int32_t bits
     if (rc) return rc;
     if (V == 0) return LLDA_OK;
     if (!n_kw || !img || !col_src || (Lp->KP & 3)) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(n_kw) & 15) || (reinterpret_cast<uintptr_t>(img) & (bits == 8 ? 3 : 7))) return LLDA_E_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(col_src) & 15) return LLDA_E_BAD_ARG;
+    if (misaligned(15, n_kw) || misaligned(bits == 8 ? 3 : 7, img)) return LLDA_E_BAD_ARG;
+    if (misaligned(15, col_src)) return LLDA_E_BAD_ARG;
     int64_t blocks = V < 256 * 32 ? V : 256 * 32;
     const dim3 grid((unsigned)blocks), block(256);
     const size_t lds = (size_t)Lp->KP * sizeof(int);
     if (bits == 8) hipLaunchKernelGGL(llda_pack_image_cols_kernel<8>, grid, block, lds, (hipStream_t)stream, n_kw, col_src, img, V, Lp->KP);
     else hipLaunchKernelGGL(llda_pack_image_cols_kernel<16>, grid, block, lds, (hipStream_t)stream, n_kw, col_src, img, V, Lp->KP);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_pack_rows16_all(const int32_t *n_kw, int64_t V, int32_t K, uint16_t *n_kw16, uint8_t *row16, void *stream)
@@ -860,7 +649,7 @@ int llda_pack_rows16_all(const int32_t *n_kw, int64_t V, int32_t K, uint16_t *n_
     if (!llda_quad_ok(K)) return LLDA_E_BAD_K;
     if (V == 0) return LLDA_OK;
     if (!n_kw || !row16 || !n_kw16) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(n_kw16) | reinterpret_cast<uintptr_t>(n_kw)) & 15) return LLDA_E_BAD_ARG;
+    if (misaligned(15, n_kw16, n_kw)) return LLDA_E_BAD_ARG;
     const int64_t blocks = (V * 2 * Lp->G + 255) / 256;
     if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
     const dim3 grid((unsigned)blocks), block(256);
@@ -868,8 +657,7 @@ int llda_pack_rows16_all(const int32_t *n_kw, int64_t V, int32_t K, uint16_t *n_
     if (Lp->G == 32) hipLaunchKernelGGL(llda_pack_rows16_all_kernel<32>, grid, block, 0, st, n_kw, n_kw16, row16, V);
     else if (Lp->G == 16) hipLaunchKernelGGL(llda_pack_rows16_all_kernel<16>, grid, block, 0, st, n_kw, n_kw16, row16, V);
     else hipLaunchKernelGGL(llda_pack_rows16_all_kernel<8>, grid, block, 0, st, n_kw, n_kw16, row16, V);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_pack_image(const int32_t *n_kw, int64_t n, int32_t bits, void *img, void *stream)
@@ -877,7 +665,7 @@ int llda_pack_image(const int32_t *n_kw, int64_t n, int32_t bits, void *img, voi
     if (n < 0 || (n & 3) || (bits != 8 && bits != 16)) return LLDA_E_BAD_ARG;
     if (n == 0) return LLDA_OK;
     if (!n_kw || !img) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(n_kw) & 15) || (reinterpret_cast<uintptr_t>(img) & (bits == 8 ? 3 : 7))) return LLDA_E_BAD_ARG;
+    if (misaligned(15, n_kw) || misaligned(bits == 8 ? 3 : 7, img)) return LLDA_E_BAD_ARG;
     const int64_t n4 = n / 4;
     int64_t blocks = (n4 + 255) / 256;
     if (blocks > 256 * 64) blocks = 256 * 64;
@@ -886,23 +674,21 @@ int llda_pack_image(const int32_t *n_kw, int64_t n, int32_t bits, void *img, voi
         hipLaunchKernelGGL(llda_pack_image_kernel<8>, grid, block, 0, (hipStream_t)stream, reinterpret_cast<const int4 *>(n_kw), img, n4);
     else
         hipLaunchKernelGGL(llda_pack_image_kernel<16>, grid, block, 0, (hipStream_t)stream, reinterpret_cast<const int4 *>(n_kw), img, n4);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_apply_delta(int32_t *counts, int32_t *delta, int64_t n, void *stream)
 {
     if (!counts || !delta || n < 0) return LLDA_E_BAD_ARG;
     if (n == 0) return LLDA_OK;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(delta)) & 15) == 0;
+    const bool aligned = !misaligned(15, counts, delta);
     const int64_t n4 = aligned ? n / 4 : 0;
     int64_t blocks = (n4 + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(llda_apply_delta_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        counts, delta, n4, n);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_count_init(const int64_t *doc_off, const int32_t *word, const int32_t *freq, const int32_t *z,
@@ -924,8 +710,7 @@ int llda_count_init(const int64_t *doc_off, const int32_t *word, const int32_t *
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(llda_count_init_kernel, dim3((unsigned)blocks), dim3(64 * waves), lds,
                        (hipStream_t)stream, doc_off, word, freq, z, D, L.KP, n_dk, n_kw, n_k);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_count_hist(const int32_t *counts, int64_t rows, int32_t K, const uint16_t *lab_mask, int32_t mask_per_row, int32_t n_bins,
@@ -938,9 +723,7 @@ int llda_count_hist(const int32_t *counts, int64_t rows, int32_t K, const uint16
     if (rc) return rc;
     const llda_layout &L = *Lp;
     if (rows == 0) return LLDA_OK;
-    if ((reinterpret_cast<uintptr_t>(counts) & 15) || (reinterpret_cast<uintptr_t>(lab_mask) & 1) ||
-        ((reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(over_n)) & 7) || (reinterpret_cast<uintptr_t>(over_val) & 3))
-        return LLDA_E_BAD_ARG;
+    if (misaligned(15, counts) || misaligned(1, lab_mask) || misaligned(7, hist, over_n) || misaligned(3, over_val)) return LLDA_E_BAD_ARG;
     if (rows > INT64_MAX / L.KP) return LLDA_E_BAD_ARG;
     HParams P;
     P.counts = reinterpret_cast<const int4 *>(counts);
@@ -965,8 +748,7 @@ int llda_count_hist(const int32_t *counts, int64_t rows, int32_t K, const uint16
     if (L.T % 4 == 0) hipLaunchKernelGGL(llda_count_hist_kernel<4>, grid, block, 0, st, P);
     else if (L.T == 2) hipLaunchKernelGGL(llda_count_hist_kernel<2>, grid, block, 0, st, P);
     else hipLaunchKernelGGL(llda_count_hist_kernel<1>, grid, block, 0, st, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_rank_labels(const llda_rank_args *a, void *stream)
@@ -976,12 +758,8 @@ int llda_rank_labels(const llda_rank_args *a, void *stream)
     if (a->D < 0 || a->first < 0 || a->first >= a->K || a->ld < a->K || a->top_n < 0 || a->top_n > 16) return LLDA_E_BAD_ARG;
     if (a->D == 0) return LLDA_OK;
     if (!a->score || a->D > INT64_MAX / a->ld) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(a->score) | reinterpret_cast<uintptr_t>(a->top_val) | reinterpret_cast<uintptr_t>(a->auc) |
-         reinterpret_cast<uintptr_t>(a->f1)) & 7)
-        return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(a->top_idx) | reinterpret_cast<uintptr_t>(a->n_thr) | reinterpret_cast<uintptr_t>(a->hit_rank) |
-         reinterpret_cast<uintptr_t>(a->flags)) & 3)
-        return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->score, a->top_val, a->auc, a->f1)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->top_idx, a->n_thr, a->hit_rank, a->flags)) return LLDA_E_BAD_ARG;
     RankParams P;
     P.score = a->score; P.truth = a->truth;
     P.D = a->D; P.ld = a->ld;
@@ -1001,8 +779,7 @@ int llda_rank_labels(const llda_rank_args *a, void *stream)
 #undef LLDA_RANK
     default: return LLDA_E_BAD_K;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 // the geometry of llda_top_words: row phases of a workgroup, workgroups across a row, partial lists per column
@@ -1036,9 +813,7 @@ int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t
     const llda_layout *Lp = layout_of(K, &rc);
     if (rc) return rc;
     const llda_layout &L = *Lp;
-    if ((reinterpret_cast<uintptr_t>(n_kw) & 15) || (reinterpret_cast<uintptr_t>(scratch) & 7) ||
-        ((reinterpret_cast<uintptr_t>(top_idx) | reinterpret_cast<uintptr_t>(top_cnt)) & 3))
-        return LLDA_E_BAD_ARG;
+    if (misaligned(15, n_kw) || misaligned(7, scratch) || misaligned(3, top_idx, top_cnt)) return LLDA_E_BAD_ARG;
     TopwParams P;
     memset(&P, 0, sizeof P);
     int32_t col_blocks;
@@ -1061,8 +836,7 @@ int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t
     else if (n <= 10) LLDA_TOPW(10)
     else LLDA_TOPW(16)
 #undef LLDA_TOPW
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64_t V, int32_t K, int32_t n,
@@ -1072,9 +846,8 @@ int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64
     if (K < 1 || K > LLDA_MAX_K) return LLDA_E_BAD_K;
     if (D == 0) return LLDA_OK;
     if (!doc_off || !word || !memb_off || !memb || !co) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(doc_off) | reinterpret_cast<uintptr_t>(co)) & 7) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(word) | reinterpret_cast<uintptr_t>(memb_off) | reinterpret_cast<uintptr_t>(memb)) & 3)
-        return LLDA_E_BAD_ARG;
+    if (misaligned(7, doc_off, co)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, word, memb_off, memb)) return LLDA_E_BAD_ARG;
     CoocParams P;
     P.doc_off = doc_off; P.word = word; P.memb_off = memb_off; P.memb = memb; P.co = co;
     P.D = D; P.V = V; P.K = K; P.n = n; P.words = (K + 1) / 2;
@@ -1092,8 +865,7 @@ int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64
         const int64_t cap = COOC_AGG_BLOCKS / slices > 1 ? COOC_AGG_BLOCKS / slices : 1;
         if (bx > cap) bx = cap;
         hipLaunchKernelGGL(llda_word_cooc_agg_kernel, dim3((unsigned)bx, (unsigned)slices), dim3(64 * COOC_WAVES), lds, st, P);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        return launched();
     }
     const size_t lds = (size_t)COOC_WAVES * P.words * sizeof(uint32_t);      // at most 61 504 bytes
     const int rl = allow_lds(llda_word_cooc_kernel, lds);
@@ -1101,8 +873,7 @@ int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64
     int64_t blocks = (D + COOC_WAVES - 1) / COOC_WAVES;
     if (blocks > LLDA_COOC_MAX_WAVES / COOC_WAVES) blocks = LLDA_COOC_MAX_WAVES / COOC_WAVES;
     hipLaunchKernelGGL(llda_word_cooc_kernel, dim3((unsigned)blocks), dim3(64 * COOC_WAVES), lds, st, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_heldout_loglik(const llda_heldout_args *a, void *stream)
@@ -1113,11 +884,8 @@ int llda_heldout_loglik(const llda_heldout_args *a, void *stream)
     if (a->D == 0) return LLDA_OK;
     if (!a->doc_off || !a->word || !a->theta || !a->phi_t) return LLDA_E_BAD_ARG;
     if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(a->doc_off) | reinterpret_cast<uintptr_t>(a->theta) | reinterpret_cast<uintptr_t>(a->phi_t) |
-         reinterpret_cast<uintptr_t>(a->mant) | reinterpret_cast<uintptr_t>(a->expo) | reinterpret_cast<uintptr_t>(a->tok) |
-         reinterpret_cast<uintptr_t>(a->bad)) & 7)
-        return LLDA_E_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(a->word) | reinterpret_cast<uintptr_t>(a->freq)) & 3) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->theta, a->phi_t, a->mant, a->expo, a->tok, a->bad)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->word, a->freq)) return LLDA_E_BAD_ARG;
     HeldoutParams P;
     P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.theta = a->theta; P.phi_t = a->phi_t;
     P.D = a->D; P.V = a->V; P.ld_theta = a->ld_theta; P.ld_phi = a->ld_phi; P.K = a->K;
@@ -1142,8 +910,7 @@ int llda_heldout_loglik(const llda_heldout_args *a, void *stream)
         else if (K <= 1024) hipLaunchKernelGGL((llda_heldout_wave_kernel<16, 2>), grid, block, 0, st, P);
         else hipLaunchKernelGGL(llda_heldout_wide_kernel, grid, block, 0, st, P);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab_mask, const int32_t *n_dk,
@@ -1168,16 +935,9 @@ int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab
         const int rl = allow_lds(llda_loglik_wide_kernel, lds);
         if (rl) return rl;
         hipLaunchKernelGGL(llda_loglik_wide_kernel, dim3(wide_blocks(D)), dim3(64), lds, st, W);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        return launched();
     }
-    switch (L.G) {
-    case 8: return dispatch_loglik_T<8>(L.T, P, st);
-    case 16: return dispatch_loglik_T<16>(L.T, P, st);
-    case 32: return dispatch_loglik_T<32>(L.T, P, st);
-    case 64: return dispatch_loglik_T<64>(L.T, P, st);
-    }
-    return LLDA_E_BAD_K;
+    return visit_layout(L.G, L.T, [&](auto g, auto t) { return launch_loglik<g.value, t.value>(P, st); });
 }
 
 static void readout_layout(const llda_layout &L, RParams &P)
@@ -1201,8 +961,7 @@ int llda_readout_phi(const int32_t *n_kw, const int32_t *n_k, const double *den,
     P.n_kw = n_kw; P.n_k = n_k; P.den = den; P.out = out; P.flags = flags; P.V = V; P.mode = mode;
     P.beta = beta; P.vbeta = (double)V * beta; P.keep = keep; P.share = share;
     hipLaunchKernelGGL(llda_readout_phi_kernel, dim3((unsigned)((V + 63) / 64)), dim3(256), 0, (hipStream_t)stream, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 int llda_readout_theta(const int32_t *n_dk, const uint16_t *lab_mask, int64_t D, int32_t K, double alpha, int32_t mode,
@@ -1226,8 +985,7 @@ int llda_readout_theta(const int32_t *n_dk, const uint16_t *lab_mask, int64_t D,
         const int rl = allow_lds(llda_readout_theta_wide_kernel, lds);
         if (rl) return rl;
         hipLaunchKernelGGL(llda_readout_theta_wide_kernel, dim3(wide_blocks(D)), dim3(64), lds, (hipStream_t)stream, W);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        return launched();
     }
     RParams P;
     memset(&P, 0, sizeof P);
@@ -1236,13 +994,7 @@ int llda_readout_theta(const int32_t *n_dk, const uint16_t *lab_mask, int64_t D,
     P.keep = keep; P.share = share;
     hipStream_t st = (hipStream_t)stream;
     const bool has_tail = L.tail != 0;
-    switch (L.G) {
-    case 8: return dispatch_theta_T<8>(L.T, P, has_tail, st);
-    case 16: return dispatch_theta_T<16>(L.T, P, has_tail, st);
-    case 32: return dispatch_theta_T<32>(L.T, P, has_tail, st);
-    case 64: return dispatch_theta_T<64>(L.T, P, has_tail, st);
-    }
-    return LLDA_E_BAD_K;
+    return visit_layout(L.G, L.T, [&](auto g, auto t) { return launch_theta<g.value, t.value>(P, has_tail, st); });
 }
 
 int llda_foldin(const llda_foldin_args *a, void *stream)
@@ -1283,16 +1035,9 @@ int llda_foldin(const llda_foldin_args *a, void *stream)
         rl = allow_lds(llda_foldin_wide_kernel, (size_t)L.KP * 12);
         if (rl) return rl;
         hipLaunchKernelGGL(llda_foldin_wide_kernel, dim3(wide_blocks(P.D)), dim3(64), (size_t)L.KP * 12, st, W);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LLDA_OK : hip_fail(e);
+        return launched();
     }
-    switch (L.G) {
-    case 8: return dispatch_foldin_T<8>(L.T, P, has_tail, st);
-    case 16: return dispatch_foldin_T<16>(L.T, P, has_tail, st);
-    case 32: return dispatch_foldin_T<32>(L.T, P, has_tail, st);
-    case 64: return dispatch_foldin_T<64>(L.T, P, has_tail, st);
-    }
-    return LLDA_E_BAD_K;
+    return visit_layout(L.G, L.T, [&](auto g, auto t) { return launch_foldin<g.value, t.value>(P, has_tail, st); });
 }
 
 int llda_selftest_div(uint64_t seed, int64_t n, unsigned long long *mismatches_dev, void *stream)
@@ -1304,8 +1049,7 @@ int llda_selftest_div(uint64_t seed, int64_t n, unsigned long long *mismatches_d
     if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
     hipLaunchKernelGGL(llda_selftest_div_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        seed, iters, mismatches_dev);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LLDA_OK : hip_fail(e);
+    return launched();
 }
 
 }  // extern "C"
