@@ -59,7 +59,10 @@
 #else
 #define LLDA_INFO_BUDGET_MARKS 0
 #endif
-#if defined(LLDA_QUAD_PRIO) || defined(LLDA_QUAD_PARTS)    // (the A/B switches of the quad kernel's site loop share the bit)
+#ifdef LLDA_QUAD_PARTS
+#error "LLDA_QUAD_PARTS is gone: kernel_quad.hpp states the one form of the site loop that ships (the former value 55)"
+#endif
+#ifdef LLDA_QUAD_PRIO
 #define LLDA_INFO_QUAD_PRIO LLDA_BUILD_QUAD_PRIO
 #else
 #define LLDA_INFO_QUAD_PRIO 0

@@ -1,15 +1,14 @@
-// kernel_quad.hpp -- llda_sweep_quad_kernel: the K = 512 dense kernel with FOUR documents per wavefront
+// kernel_quad.hpp -- llda_sweep_quad_kernel: the dense kernel of the layouts with 16 slots per lane, four documents per wavefront at
+// K = 512 (eight / sixteen at K = 256 / 128), and llda_pack_rows16_all, the 16-bit image of n_kw it reads
 // Part of the single translation unit llda_gibbs.hip (included in order; see the contents list there).
 #pragma once
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// Why.  llda_sweep_kernel<32,16,..,R16,W4> (kernel_sweep.hpp) is bound by instruction issue: 84 vector instructions per site of
-// which 20 are the arithmetic of the 512 scores (profiles/r05_site_loop_budget.md); the other ~130 per wavefront iteration -- lane scan,
-// threshold, search, pick, count update, addresses, commit -- are paid once per iteration whatever the number of documents in the
-// wavefront.  Here a document is walked by 16 lanes x 32 slots, four documents per wavefront: the fixed part is shared by four sites.
-// LDS holds the same 4 KB per document, so a CU holds the same 32 documents -- in 8 wavefronts (two per SIMD, 256 VGPRs) instead of 16.
+// Why.  llda_sweep_kernel<32,16,..,R16,W4> (kernel_sweep.hpp) is bound by instruction issue: 84 vector instructions per site, of which
+// 20 are the arithmetic of the 512 scores (profiles/r05_site_loop_budget.md); the other ~130 per wavefront iteration -- lane scan, threshold,
+// search, pick, count update, addresses, commit -- are paid once per iteration whatever the number of documents in the wavefront.  Here a
+// document is walked by 16 lanes x 32 slots, four documents per wavefront (the same 4 KB of LDS per document, two wavefronts per SIMD).
 //
 // Geometry.  The layout of K = 512 is 32 lanes x 16 slots (llda_layout: G = 32, T = 16).  Quad lane lq plays the standard lanes
 // 2 lq and 2 lq + 1 one after the other, so the draw order (standard lane, slot) is unchanged:
@@ -18,15 +17,12 @@ namespace {
 //                         standard lane 2 lq) and of chain B (those of lane 2 lq + 1): one packed fma advances both chains
 // Rows come from the 16-bit image of n_kw (llda_pack_rows16_all: EVERY row, with a per-row flag "all counts fit" decided per sweep);
 // a site whose row does not fit reads the int32 row without prefetch.  Documents of at most 65 535 tokens (n_dk packed with its
-// sweep-start value, as the W4 form).
+// sweep-start value, as the W4 form).  K = 256 / 128 (eight / sixteen documents per wavefront): QuadGeo below.
 //
 // Tier 0 with two chains of 16 per lane: every prefix within (12 + 16) v of the lane's share, the lane total one more,
 // four scan steps: X and the total within 33 v, the target fl(u~ tot~ - X~[g-1]) (one fma) within 69.2 v, its bounds 70.2 v; chain A is
-// compared directly (98.2 v), chain B against the bounds minus chain A's total (99.2 v) -- inside the 105 v of the 2-document kernel,
-// margin 128 v.  Int32 rows with counts >= 2^24: + 2 v.
-// ---------------------------------------------------------------------------------------------
-// LLDA_MARGIN0_QUAD (sweep_plan.hpp): the tier-0 margin of this kernel relative to the total, 104 * 2^-24 (bound 99.2 v, 101.2 v with
-// int32 counts >= 2^24) -- what the test hooks scale; production uses the sharper form below
+// compared directly (98.2 v), chain B against the bounds minus chain A's total (99.2 v; 101.2 v with int32 counts >= 2^24).
+// LLDA_MARGIN0_QUAD (sweep_plan.hpp), the margin relative to the total on that bound, is 104 * 2^-24: what the test hooks scale.
 // The data-dependent margin (production).  With v = 2^-24 and true values L (lane total), P (the lanes before), t = u * total, the
 // compared difference  q~[s] - (tg~ -+ m)  is off by at most
 //     28.1 v L  (prefix: 12 v of the terms + 16 roundings)  + 1 v L (chain B against the bounds minus chain A's total)
@@ -41,54 +37,35 @@ namespace {
 constexpr float QM_L = 1.05f * 32.0f * 0x1p-24f, QM_T = 1.05f * 39.0f * 0x1p-24f, QM_P = 1.05f * 37.0f * 0x1p-24f, QM_TOT = 1.05f * 0.25f * 0x1p-24f;
 #define QLDS(arr, rho, t) (arr)[(rho) >> 2][t][(rho) & 3]      // the per-document LDS arrays, see the kernel
 constexpr int QT = 32;        // slots per quad lane
-// Issue priority by phase of an iteration (s_setprio; round 6).  The two wavefronts of a SIMD run the same code on documents of the same
-// length: left alone they drift into the SAME phase and compete for the vector unit in the bulk phases while both wait in the dependent
-// ones.  A wavefront raises its priority for the independent bulk of an iteration -- from the scalar loads / LDS reads of the count
-// update through the next site's own-count removal, conversion and row prefetch, the update's arithmetic and the commit (QP_BULK), and
-// for the factor reads and the chains of the next site (QP_TOP) -- and drops it for the dependent decision (lane scan, threshold,
-// search, key minimum, cold tiers, decode: QP_DEC): the wavefront in its bulk gets the issue slots, the other one's dependent chain
-// fills the gaps, and the two stay in antiphase.  configs[3]: 9.39 -> 8.66 ms per 250 000 documents (- 7.7 %), K = 256 - 1.5 %, K = 128
-// - 0.4 %; placements measured: profiles/r06_site_loop_budget.md.  -DLLDA_QUAD_PRIO=tdb (three digits) overrides (llda_build_info bit).
+// Issue priority by phase of an iteration (s_setprio).  The two wavefronts of a SIMD run the same code on documents of the same length:
+// left alone they drift into the SAME phase, compete for the vector unit in the bulk phases and both wait in the dependent ones.  A
+// wavefront raises its priority for the independent bulk (QP_BULK: from the scalar loads / LDS reads of the count update through the next
+// site's own-count removal, conversion and row prefetch to the commit) and for the factor reads and chains of the next site (QP_TOP), and
+// drops it for the dependent decision (QP_DEC: lane scan, threshold, search, key minimum, cold tiers, decode): the two stay in antiphase.
+// configs[3]: 9.39 -> 8.66 ms per 250 000 documents (- 7.7 %), K = 256 - 1.5 %, K = 128 - 0.4 %; placements measured:
+// profiles/r06_site_loop_budget.md.  -DLLDA_QUAD_PRIO=tdb (three digits) overrides (llda_build_info bit).
 #ifdef LLDA_QUAD_PRIO
 constexpr int QP_TOP = (LLDA_QUAD_PRIO) / 100 % 10, QP_DEC = (LLDA_QUAD_PRIO) / 10 % 10, QP_BULK = (LLDA_QUAD_PRIO) % 10;
 #else
 constexpr int QP_TOP = 3, QP_DEC = 0, QP_BULK = 2;
 #endif
 constexpr int QNT = 128;      // threads per workgroup: two wavefronts, eight documents
-// What the site loop does not carry into the dependent phase of every iteration (each part on its own bit, for A/B builds; the
-// production build has 1, 2, 4 (profiles/r07_quad_full_loop.md), 16 and 32 (profiles/r08_quad_entry_key.md); -DLLDA_QUAD_PARTS=m
-// overrides and sets the LLDA_QUAD_PRIO bit of llda_build_info):
-//   1  FULL form of the site: while every document of the wavefront still has the sites n .. n + 3, "this document has ended" (act,
-//      more, the clamp of the look-ahead offsets) is the constant true -- the masked form runs the rest up to the longest document
-//   2  the test hooks on the margins (llda_sweep_args.debug_margin != 0) are a template parameter: production computes m directly
-//   4  z of a site is read THREE sites ahead, with the word id (which then serves as the site's word: one load less per iteration),
-//      so the old position of site n+2 is decoded in the bulk phase of iteration n from a value that landed an iteration ago --
-//      not in the dependent phase of iteration n+1 behind a wait
-// and the bookkeeping around the draw that turned a slot number into addresses again and again (profiles/r08_quad_entry_key.md):
-//   8  NOT in the production build (measured: nothing at K = 512 inside the combination, + 0.6 % / + 0.9 % at K = 256 / 128; the
-//      compiler already makes the address from rho in four instructions): a slot travels as its ENTRY (quad_entry below: the LDS
-//      byte offsets the slot number stands for) -- in the key of the draw, in QuadSite::so, into the count update (one AND gives the
-//      offset of the slot in s_ndk) and into the own-count removal (one AND gives the row of s_hot)
-//  16  the old position of a site is decoded by a table in LDS (s_ent[position] = the slot as it travels) instead of seven bit operations
-//  32  the "one lane owns both" branch tests its mask on the scalar unit, the log store takes the SGPR base + 32-bit offset form of the
-//      z store (positions below 2^30: llda_sweep), the own count goes into the 24-bit multiply-add without a separate sign extension
-#ifdef LLDA_QUAD_PARTS
-constexpr int QUAD_PARTS = (LLDA_QUAD_PARTS);
-#else
-constexpr int QUAD_PARTS = 55;
-#endif
-constexpr bool QUAD_FULL_LOOP = (QUAD_PARTS & 1) != 0, QUAD_HOOKS_OUT = (QUAD_PARTS & 2) != 0, QUAD_EARLY_DECODE = (QUAD_PARTS & 4) != 0;
-constexpr bool QUAD_ENTRY = (QUAD_PARTS & 8) != 0, QUAD_TABLE = (QUAD_PARTS & 16) != 0, QUAD_SMALL = (QUAD_PARTS & 32) != 0;
+// The site loop (what each part bought: DESIGN.md 4.1a and the profiles of rounds 7 and 8 it names):
+//   - two forms of a site.  FULL: while every document of the wavefront still has the sites n .. n + 3, "this document has ended" (act,
+//     more, the clamp of the look-ahead offsets) is the constant true; the masked form runs the rest up to the longest document
+//   - the test hooks on the margins (llda_sweep_args.debug_margin != 0) are the template parameter HOOKS: production computes m directly
+//   - word id and z of a site are read THREE sites ahead, into the register set of the site just decided: the old position of site n+2
+//     is decoded in the bulk phase of iteration n from a value that landed an iteration ago, not in the dependent phase behind a wait
+//   - the old position is decoded through a table in LDS (s_ent[position] = its slot number) instead of seven bit operations
+//   - "one lane owns both" is tested on the scalar unit; the log store takes the SGPR base + (csc_pos << 2) form of the z store
 template <bool B> struct QuadForm { static constexpr bool value = B; };     // the form of a site: QuadForm<true> = FULL
 
-// The same walk for the narrower layouts of 16 slots per lane (llda_layout: T = 16): a document is LPD = 2^LB lanes x 32 slots, 64 / LPD
-// documents per wavefront --
+// The same walk for every layout of 16 slots per lane (llda_layout: T = 16): a document is LPD = 2^LB lanes x 32 slots --
 //     LB = 4   K = 512 (G = 32): 4 documents per wavefront      LB = 3   K = 256 (G = 16): 8      LB = 2   K = 128 (G = 8): 16
 //     device position     pos   = i << (3 + LB) | lq << 3 | e << 2 | c
-// Everything per lane (chains, search, count update, LDS layout) is the same code; the cross-lane steps stay inside the LPD lanes of a
-// document (scan steps masked at the document's first lanes, totals and the minimum by xor butterflies), the random bits come 2 LPD
-// sites at a time, and the site's own count leaves the PACKED 16-bit row by compare-and-subtract (sixteen documents would mean sixteen
-// indexed writes).  The error bound of tier 0 only shrinks (fewer scan steps), the constants below are kept.
+// Everything per lane (chains, search, count update, own-count removal, LDS layout) is the same code; the cross-lane steps stay inside the
+// LPD lanes of a document (scan steps masked at the document's first lanes, totals and the minimum by xor butterflies) and the random
+// bits come 2 LPD sites at a time.  The error bound of tier 0 only shrinks (fewer scan steps), the constants above are kept.
 template <int LB>
 struct QuadGeo {
     static constexpr int LPD = 1 << LB;            // lanes per document
@@ -104,36 +81,12 @@ template <int LB>
 __device__ __forceinline__ int quad_rho(int pos) { return ((pos >> LB) & 0x18) | ((pos & 3) << 1) | ((pos >> 2) & 1); }
 constexpr int quad_rho_of(int i, int e, int c) { return 8 * i + 2 * c + e; }
 
-// How a slot TRAVELS (key of the draw, QuadSite::so, the argument of the count update): as the slot number rho (production) or,
-// QUAD_ENTRY, as its entry -- the byte offsets that the slot number rho stands for, each bit of rho in two places --
-//     bits 2, 3, 11 .. 13   (rho >> 2) * 2048 + (rho & 3) * 4 = byte offset of QLDS(arr, rho, 0) inside s_ndk / s_pa   (QE_NDK)
-//     bits 6 .. 10          rho << 6                          = byte offset of row rho of s_hot                        (QE_HOT)
-// so that a consumer masks where it shifted, masked and added before.  Every bit of rho maps to its own bits of the entry: the entry of
-// an OR of slot bits is the OR of their entries, which is how the search of quad_draw builds it (tests/test_quad_entry_encoding.py).
-constexpr uint32_t QE_NDK = 0x380Cu, QE_HOT = 0x7C0u;
-constexpr uint32_t quad_entry(uint32_t rho) { return ((rho >> 2) * 2048u + (rho & 3u) * 4u) | rho << 6; }
-constexpr uint32_t quad_slot(uint32_t rho) { return QUAD_ENTRY ? quad_entry(rho) : rho; }
-constexpr int QS_BITS = QUAD_ENTRY ? 14 : 5;                // width of a travelling slot
-constexpr int QK_LANE = 9 + QS_BITS;                        // key = quad lane << QK_LANE | slot << 9 | position: the minimum orders by lane first
-constexpr uint32_t QK_ZN = (1u << QK_LANE) - 1;             // slot << 9 | position
+// A slot travels (key of the draw, QuadSite::so, the argument of the count update) as its slot number rho.
+constexpr int QK_LANE = 14;                                 // key = quad lane << QK_LANE | rho << 9 | position: the minimum orders by lane first
+constexpr uint32_t QK_ZN = (1u << QK_LANE) - 1;             // rho << 9 | position
 // no slot above lo: the last slot of the last lane, under a lane field no lane has -- the largest key
-template <int LB> constexpr uint32_t QUAD_KEY_NONE = 0x3Fu << QK_LANE | quad_slot(31) << 9 | (uint32_t)(QuadGeo<LB>::KP - 1);
-constexpr bool quad_entry_ok()
-{
-    uint32_t seen_or = 0;
-    for (uint32_t r = 0; r < 32; ++r) {
-        const uint32_t en = quad_entry(r);
-        if ((en & ~(QE_NDK | QE_HOT)) || (en & QE_HOT) != r << 6 || (en & QE_NDK) != (r >> 2) * 2048u + (r & 3u) * 4u) return false;
-        for (uint32_t q = 0; q < r; ++q)
-            if (quad_entry(q) == en) return false;
-        if (quad_entry(r | 1u) != (en | quad_entry(1)) || quad_entry(r | 8u) != (en | quad_entry(8))) return false;
-        seen_or |= en;
-    }
-    return seen_or == (QE_NDK | QE_HOT);
-}
-static_assert((QE_NDK & QE_HOT) == 0, "the two fields of an entry do not overlap");
-static_assert(quad_entry_ok(), "quad_entry: injective on 0 .. 31, each field recovers its offset, OR of slots = OR of entries");
-static_assert(quad_entry(31) < (1u << 14) && (0x3Fu << QK_LANE | QK_ZN) <= 0x7FFFFFFFu, "the key fits 31 bits");
+template <int LB> constexpr uint32_t QUAD_KEY_NONE = 0x3Fu << QK_LANE | 31u << 9 | (uint32_t)(QuadGeo<LB>::KP - 1);
+static_assert((0x3Fu << QK_LANE | QK_ZN) <= 0x7FFFFFFFu, "the key fits 31 bits");
 
 // minimum of a key over the lanes of a document, in every lane: one DPP instruction per step (the compiler's form is three)
 template <int LB>
@@ -200,8 +153,7 @@ typedef float q_v32f __attribute__((ext_vector_type(32)));
 // Tier 0 for all documents of the wavefront at once.  xv = the row minus the site's own count (fp32, exact), pa = the cached factors, both in slot
 // order rho: the pair (2a, 2a+1) holds element a of chain A and of chain B, so ONE packed instruction advances both chains.
 // Returns the wavefront's ballot of the lanes that are not sure; zn = the position every lane's document drew.
-// margin_rel, margin_data: m = total * margin_rel + margin_data * (the data-dependent form): production (0, 1), test hooks (2^-n or 2, 0)
-// HOOKS = false: m = the data-dependent form itself (what (0, 1) gives bit for bit: fl(tot * 0 + 1 * md) = md), nothing read or multiplied
+// HOOKS: m = total * margin_rel + margin_data * (the data-dependent form md); else m = md, what production's (0, 1) gives bit for bit
 // PAD (K < KP): "no slot above lo in any lane" names position KP - 1, which holds no topic there -- the margin makes that outcome
 // impossible for a sure site (the last lane's last TOPIC has the total as its prefix), but a test hook or a later change of the margin
 // must not be able to write a topic-less position: the document is reported as not sure, and the exact tier's masked fallback decides.
@@ -288,13 +240,12 @@ __device__ __forceinline__ uint64_t quad_draw(const q_v32f &xv, const q_v2f (&pa
     uint64_t bad_total;
     asm("v_cmp_class_f32_e64 %0, %1, %2" : "=s"(bad_total) : "v"(tot - margin), "v"(0x2FF));
     uint64_t unsure = __ballot(!(ub > hi)) | bad_total;
-    // the position this lane would name, keyed by its lane; the document's first lane with a slot above lo wins (none: 511, the
-    // last slot of the last lane).  Row-wide minimum: four DPP steps, one instruction each (the compiler's form is three)
-    // key = lane << QK_LANE | slot << 9 | position: every search outcome sets its bit of the position AND its bits of the travelling slot
+    // the position this lane would name, keyed by its lane; the document's first lane with a slot above lo wins (none: QUAD_KEY_NONE).
+    // key = lane << QK_LANE | rho << 9 | position: every search outcome sets its bit of the position AND its bit of the slot number
     LLDA_MARK("pick");
     constexpr uint32_t I1 = 2u << QuadGeo<LB>::IS, I0 = 1u << QuadGeo<LB>::IS;
-    const uint32_t p = (c1 ? (I1 | quad_slot(16) << 9) : 0u) | (c2 ? (I0 | quad_slot(8) << 9) : 0u) | (c3 ? (2u | quad_slot(4) << 9) : 0u) |
-                       (c4 ? (1u | quad_slot(2) << 9) : 0u) | (c0 ? (4u | quad_slot(1) << 9) : 0u) | ((uint32_t)lq << 3) | ((uint32_t)lq << QK_LANE);
+    const uint32_t p = (c1 ? (I1 | 16u << 9) : 0u) | (c2 ? (I0 | 8u << 9) : 0u) | (c3 ? (2u | 4u << 9) : 0u) |
+                       (c4 ? (1u | 2u << 9) : 0u) | (c0 ? (4u | 1u << 9) : 0u) | ((uint32_t)lq << 3) | ((uint32_t)lq << QK_LANE);
     uint32_t key = c5 ? QUAD_KEY_NONE<LB> : p;              // (no slot above lo: the last slot of the last lane wins only if no lane has one)
     key = quad_min_key<LB>(key);
     zn = (int)(key & QK_ZN);                                // slot << 9 | position; the lane is position >> 3 & (LPD - 1)
@@ -345,7 +296,7 @@ __device__ __forceinline__ uint64_t quad_tier1(const q_v32f &xv, const int (*s_n
     // position of chain index cnt_lo: e = k >> 4, i = (k >> 2) & 3, c = k & 3
     const uint32_t k = (uint32_t)cnt_lo;
     const uint32_t i_ = (k >> 2) & 3u, e_ = (k >> 4) & 1u, c_ = k & 3u;
-    const uint32_t p = (i_ << QuadGeo<LB>::IS) | ((uint32_t)lq << 3) | (e_ << 2) | c_ | (quad_slot(8u * i_ + 2u * c_ + e_) << 9) | ((uint32_t)lq << QK_LANE);
+    const uint32_t p = (i_ << QuadGeo<LB>::IS) | ((uint32_t)lq << 3) | (e_ << 2) | c_ | ((8u * i_ + 2u * c_ + e_) << 9) | ((uint32_t)lq << QK_LANE);
     uint32_t key = cnt_lo >= QT ? QUAD_KEY_NONE<LB> : p;
     key = quad_min_key<LB>(key);
     zn = (int)(key & QK_ZN);
@@ -353,20 +304,18 @@ __device__ __forceinline__ uint64_t quad_tier1(const q_v32f &xv, const int (*s_n
     return unsure;
 }
 
-struct QuadSite { int v, f, zo, c, zn, lo, so; uint8_t w; };  // (lo, so) = quad lane and travelling slot (quad_slot) of zo; w = flag of the word's row (0: wide)
+struct QuadSite { int v, f, zo, c, zn, lo, so; uint8_t w; };  // (lo, so) = quad lane and slot number of zo; w = flag of the word's row (0: wide)
 
 // n_dk and the factors made from it, in ONE object: the factor of a slot sits at a compile-time distance from its count, so the count
 // update addresses the slot once (ds_write_b32 ... offset:)
 struct QuadDocLds {
     // [rho >> 2][thread][rho & 3]: a lane's four consecutive slots are 16 contiguous bytes, 16 bytes apart from lane to lane -- the 32
-    // factors of a lane come with 8 ds_read_b128 (conflict free) instead of 16 two-address reads
-    // (aligned: the 16-byte reads need the alignment that a __shared__ array of its own gets from the compiler)
+    // factors of a lane come with 8 ds_read_b128 (conflict free; hence the alignment) instead of 16 two-address reads
     __attribute__((aligned(16))) int ndk[QT / 4][QNT][4];      // n_dk | sweep-start n_dk << 16
     __attribute__((aligned(16))) float pa[QT / 4][QNT][4];     // tier-0 factor fl32((n_dk + alpha) / (n_k + V*beta))
 };
-static_assert(offsetof(QuadDocLds, pa) == sizeof(int) * QT * QNT && sizeof(int) * QT * QNT < 65536 &&
-              (quad_entry(31) & QE_NDK) == (7 * QNT * 4 + 3) * sizeof(int),
-              "the factor of a slot is an immediate offset away from its count; QE_NDK is the offset of QLDS(arr, rho, 0)");
+static_assert(offsetof(QuadDocLds, pa) == sizeof(int) * QT * QNT && sizeof(int) * QT * QNT < 65536,
+              "the factor of a slot is an immediate offset away from its count");
 
 // -DQUAD_PROFILE (tools/quad_phase_profile.py; never in a production build: llda_build_info reports it): wavefront 0 of workgroup 0
 // stamps the shader clock at the phase boundaries of every site and adds the differences up in status[8 + phase]
@@ -397,17 +346,16 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
     __shared__ float s_u[QNT / LPD][2 * LPD];  // the fp32 uniforms of the next 2 LPD sites of every document
     // row rho: -1 (or -65536: the upper half) in the packed register that holds slot rho, else 0 (read as v4i)
     __shared__ __attribute__((aligned(16))) int s_hot[QT][16];
-    // the travelling slot of every device position (QUAD_TABLE: decode_old reads it where it made it from the position's bits)
-    __shared__ uint16_t s_ent[QUAD_TABLE ? KP : 1];
+    __shared__ uint16_t s_ent[KP];             // the slot number of every device position (decode_old)
     // four workgroups per CU (two wavefronts per SIMD) is what the kernel is tuned for: 160 KB of LDS / 4
-    static_assert(LB != 4 || sizeof(s_nk) + sizeof(s_nk0) + sizeof(s_doc) + sizeof(s_u) + sizeof(s_hot) + (QUAD_TABLE ? sizeof(s_ent) : 0) <= 40960,
+    static_assert(LB != 4 || sizeof(s_nk) + sizeof(s_nk0) + sizeof(s_doc) + sizeof(s_u) + sizeof(s_hot) + sizeof(s_ent) <= 40960,
                   "K = 512: the static LDS of a workgroup must leave room for four workgroups on a CU");
 
     const int tid = threadIdx.x;
     for (int i = tid; i < KP; i += QNT) {
         s_nk[i] = 0;
         s_nk0[i] = P.n_k[i];
-        if constexpr (QUAD_TABLE) s_ent[i] = (uint16_t)quad_slot((uint32_t)quad_rho<LB>(i));
+        s_ent[i] = (uint16_t)quad_rho<LB>(i);
     }
     for (int i = tid; i < QT * 16; i += QNT) {
         // slot rho = 8 i + 2 c' + e sits in xp[e << 3 | (i >> 1) << 2 | (i & 1) << 1 | c' >> 1], half c' & 1 (convert_row)
@@ -428,12 +376,8 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
     typedef int v4i __attribute__((ext_vector_type(4)));
     QP_DECL;
 
-    // the count of a travelling slot in this lane's part of s_ndk; its factor sits sizeof(s_doc.ndk) bytes on (QuadDocLds)
-    char *const doc_lane = (char *)&s_doc.ndk[0][tid][0];
-    auto ndk_of = [&](int sg) -> int * {
-        if constexpr (QUAD_ENTRY) return (int *)(doc_lane + ((uint32_t)sg & QE_NDK));
-        else return &QLDS(s_doc.ndk, sg, tid);
-    };
+    // the count of slot sg in this lane's part of s_ndk; its factor sits sizeof(s_doc.ndk) bytes on (QuadDocLds)
+    auto ndk_of = [&](int sg) -> int * { return &QLDS(s_doc.ndk, sg, tid); };
     auto pa_of = [&](int *nd) -> float * { return (float *)((char *)nd + offsetof(QuadDocLds, pa)); };
     auto update = [&](int sg, int pos, int df) {
         int *const c = ndk_of(sg);
@@ -507,9 +451,8 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         auto load_scalars = [&](QuadSite &R, const uint32_t o) {
             R.v = gload_i32(word_b, o); R.f = gload_i32(freq_b, o); R.c = gload_i32(csc_b, o); R.zo = gload_i32(z_b, o);
         };
-        // LB < 4 (eight or sixteen documents per wavefront: every scalar load touches that many cache lines, and the vector-memory address
-        // pipeline becomes the bound -- TA busy 0.71 with five scalar loads per site): {word, freq, csc_pos} come as ONE 16-byte record
-        // (llda_sweep_args.site_rec), read THREE sites ahead, so that the row of site n+2 is issued from a record that has landed
+        // LB < 4 (every scalar load touches eight or sixteen cache lines, and the vector-memory address pipeline becomes the bound: TA busy
+        // 0.71 with five loads per site): {word, freq, csc_pos} come as ONE 16-byte record (llda_sweep_args.site_rec), read THREE sites ahead
         const int32_t *rec_b = REC ? P.site_rec + site_base * 4 : nullptr;
         int pv = 0, pf = 0, pc = 0;                                     // the record in flight
         auto load_rec = [&](int &v, int &f, int &c, const uint32_t o) {
@@ -518,11 +461,8 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         };
         auto decode_old = [&](QuadSite &R) {
             R.lo = (R.zo >> 3) & (LPD - 1);
-            if constexpr (QUAD_TABLE) {                              // (zo is a position, as for s_nk0[zo] in the count update)
-                R.so = s_ent[R.zo];
-                asm("" : "+v"(R.so));                                // (a full register from here on: no 16-bit value to extend again at its uses)
-            }
-            else R.so = (int)quad_slot((uint32_t)quad_rho<LB>(R.zo));
+            R.so = s_ent[R.zo];                                      // (zo is a position, as for s_nk0[zo] in the count update)
+            asm("" : "+v"(R.so));                                    // (a full register from here on: no 16-bit value to extend again at its uses)
         };
         // the 16-bit row of word v: chunks (e, j) = slots 8j .. 8j+7 of standard lane 2 lq + e, and the row's flag
         // (32-bit byte offsets from the image: llda_sweep checked V * 1024 < 2^32; a row is 2 KP bytes, its second half KP bytes on)
@@ -583,22 +523,17 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                     xv[rb_] = flag == 0 ? (float)xi[rb_] : (float)((uint32_t)xp[k] >> 16);
                 }
 #pragma unroll
-                for (int r = 0; r < QT; ++r) xv[r] -= (flag == 0 && so == (int)quad_slot(r)) ? own : 0.0f;
+                for (int r = 0; r < QT; ++r) xv[r] -= (flag == 0 && so == r) ? own : 0.0f;
             }
         };
         // The site's own count leaves the PACKED 16-bit row: the slot number so is uniform in a document, and row so of s_hot holds -1 or
-        // -65536 in the one register of the sixteen that carries the slot -- four LDS reads (the same address in every lane of a
-        // document: broadcasts) and sixteen multiply-adds, for all documents of the wavefront at once.  own = 0 in the lanes that do
-        // not hold the slot.  (Round 5 took it out of the fp32 row with a register-indexed subtract per document -- s_set_gpr_idx_on
-        // under a hand-set exec mask on pinned registers, correct only behind an s_nop found by experiment; the narrower geometries
-        // paid sixteen compare-select-subtract triples.  A row that does not fit 16 bits: see convert_row.)
+        // -65536 in the one register of the sixteen that carries the slot -- four LDS reads (broadcasts: one address per document) and
+        // sixteen multiply-adds for all documents of the wavefront at once; own = 0 in the lanes that do not hold the slot.
         auto remove_own_packed = [&](const int so, const int own) {
             LLDA_MARK("own_removal");
-            // (QUAD_SMALL: 0 <= own < 2^16, llda_sweep: max_doc_tokens -- the 24-bit multiply-add needs no sign extension in front of it)
-            if constexpr (QUAD_SMALL) __builtin_assume((uint32_t)own < 65536u);
-            const v4i *hot;
-            if constexpr (QUAD_ENTRY) hot = (const v4i *)((const char *)&s_hot[0][0] + ((uint32_t)so & QE_HOT));
-            else hot = (const v4i *)&s_hot[so][0];
+            // (0 <= own < 2^16, llda_sweep: max_doc_tokens -- the 24-bit multiply-add needs no sign extension in front of it)
+            __builtin_assume((uint32_t)own < 65536u);
+            const v4i *hot = (const v4i *)&s_hot[so][0];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const v4i h = hot[j];
@@ -609,11 +544,10 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
 
         // Software pipeline.  At the top of iteration n, xv holds the row of site n as fp32 with the site's own count taken out -- made
         // during iteration n-1, in the shadow of the LDS reads of its count update, from the row that was issued an iteration earlier
-        // still.  Scalars run two sites ahead in three rotating register sets (the loop is unrolled by three), the word ids three (wq);
-        // QUAD_EARLY_DECODE: word id AND z three ahead, loaded into the set of the site that has just been decided (the set site n+3
-        // will use), so that (lo, so) of site n+2 are made in the bulk phase of iteration n from a z that landed an iteration ago.
+        // still.  Frequency and csc_pos run two sites ahead in three rotating register sets (the loop is unrolled by three), word id
+        // and z three, in the set of the site that has just been decided (the set site n+3 will use).
         QuadSite R0, R1, R2;
-        int wq = 0;                                      // (!REC) word of site n+2 at the top of iteration n
+        int wq = 0;                                      // (!REC) word of site 2
         if constexpr (REC) {
             load_rec(R0.v, R0.f, R0.c, off_of(0)); R0.zo = gload_i32(z_b, off_of(0));
             load_rec(R1.v, R1.f, R1.c, off_of(1)); R1.zo = gload_i32(z_b, off_of(1));
@@ -623,35 +557,27 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
             load_scalars(R1, off_of(1));
             wq = gload_i32(word_b, off_of(2));
         }
-        R0.zn = R1.zn = 0;
-        R2.v = R2.f = R2.zo = R2.c = R2.zn = R2.lo = R2.so = R2.w = 0;
-        if constexpr (QUAD_EARLY_DECODE) {                             // word and z run three sites ahead, in the set of the site itself
-            R2.v = REC ? pv : wq;
-            R2.zo = gload_i32(z_b, off_of(2));
-        }
+        R0.zn = R1.zn = R2.zn = R2.f = R2.c = R2.lo = R2.so = R2.w = 0;
+        R2.v = REC ? pv : wq;                                          // word and z run three sites ahead, in the set of the site itself
+        R2.zo = gload_i32(z_b, off_of(2));
         load_row16(R0.v, R0.w);
         uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
         decode_old(R0);
-        if constexpr (QUAD_EARLY_DECODE) decode_old(R1);               // (every iteration decodes the site two ahead)
+        decode_old(R1);                                                // (every iteration decodes the site two ahead)
         if (len > 0 && lq == R0.lo) update(R0.so, R0.zo, -R0.f);      // site 0 leaves its topic (LabeledLDA.py:109-111)
         remove_own_packed(R0.so, (len > 0 && lq == R0.lo) ? R0.f : 0);
         convert_row(R0.v, R0.w, R0.so, (len > 0 && lq == R0.lo) ? (float)R0.f : 0.0f);
         load_row16(R1.v, R1.w);                                        // row of site 1
 
-        // Two forms of one site.  The masked form is the general one: act / more = "this document has site n / n + 1".  The FULL form
-        // is the masked one with act = more = true folded in and the look-ahead offsets unclamped, NOTHING else: the driver runs it
-        // only while n + 3 < minlen (iteration n loads the scalars of site n + 2 and the word of site n + 3).
+        // Two forms of one site.  The masked form is the general one: act / more = "this document has site n / n + 1".  The FULL form is
+        // that with act = more = true folded in and the look-ahead offsets unclamped, NOTHING else: it runs only while n + 3 < minlen.
         auto site = [&](auto form, const int n, QuadSite &cur, QuadSite &nxt, QuadSite &prv) {
             constexpr bool FULL = decltype(form)::value;
             const bool act = FULL || n < len, more = FULL || n + 1 < len;
             auto off = [&](int m) { if constexpr (FULL) return off_full(m); else return off_of(m); };
             const int f = cur.f, zo = cur.zo;
             QP_START();
-            if constexpr (FULL || !QUAD_FULL_LOOP) {                   // (tools/site_loop_budget.py counts the FULL form)
-                LLDA_MARK("site_top");
-            } else {
-                LLDA_MARK("site_top_masked");
-            }
+            if constexpr (FULL) { LLDA_MARK("site_top"); } else { LLDA_MARK("site_top_masked"); }     // (tools/site_loop_budget.py counts the FULL form)
             LLDA_MARK("lds_factors");
             __builtin_amdgcn_s_setprio(QP_TOP);
             q_v2f pa[16];
@@ -691,8 +617,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 const uint64_t t0_w = unsure;                          // documents tier 0 was unsure about
                 if (lq == 0 && ((t0_w >> gbase) & Geo::GM) && P.status) atomicAdd(P.status + 1, 1);   // statistics
                 int z1;
-                // (a document whose row was read as int32 skips tier 1: a count of 2^24 or more is not exact in xv)
-                // (HOOKS: a tier-1 margin >= 1 skips tier 1)
+                // (skips tier 1: a document whose row was read as int32 -- a count of 2^24 or more is not exact in xv; HOOKS: a margin >= 1)
                 uint64_t still = ((!HOOKS || P.margin_rel < 1.0 ? quad_tier1<LB, PAD>(xv, s_ndk, s_nk0, tid, lq, uniform53(ra, rb), P.alpha, P.beta, P.vbeta,
                                                                                   P.margin_rel, vm, z1) : ~0ull) | __ballot(cur.w == 0));
                 if constexpr (!FULL) still &= __ballot(act);
@@ -717,7 +642,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                         zc = zo_r;
                         if (lane == 0 && P.status) atomicOr(P.status, 1);   // no topic with positive probability
                     }
-                    zn = (row == r) ? (zc | (int)(quad_slot((uint32_t)quad_rho<LB>(zc)) << 9)) : zn;
+                    zn = (row == r) ? (zc | quad_rho<LB>(zc) << 9) : zn;
                 }
             }
             QP_MARK(2);                                                // (cold tiers)
@@ -725,24 +650,19 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
 
             // add the site back (LabeledLDA.py:121-125) and take the NEXT site out of its topic: ONE read-modify-write per lane, branch
             // free -- a lane that owns neither rewrites its slot 0 with what is there (the factor is a function of the counts) --, a
-            // second pass (rare) for the documents where one lane owns both.  The commit of this site (z and ONE log word, quad lane 0 of
-            // every document that has the site: exec mask by hand, no divergent region) and the scalar loads of site n+2 are issued in
-            // the shadow of the LDS reads.
+            // second pass (rare) for the documents where one lane owns both.  The scalar loads of the sites ahead, the front end of site
+            // n+1 and the commit (z and ONE log word, quad lane 0 of every document that has the site) follow in the shadow of its LDS reads.
             {
                 const int zpos = zn & 511, sn = zn >> 9, ln = (zn >> 3) & (LPD - 1);
                 cur.zn = zpos;
                 // the log word of the commit below, made HERE (pinned: the empty asm keeps it from sinking to its use): this site's z is
-                // dead before the scalar loads, which (QUAD_EARLY_DECODE) reuse its register for the site three ahead -- computed at the
-                // commit, the register is still live when the load is issued and the sets rotate with a move behind a vmcnt wait
+                // dead before the scalar loads, which reuse its register for the site three ahead -- computed at the commit, the
+                // register is still live when the load is issued and the sets rotate with a move behind a vmcnt wait
                 uint32_t cword = (uint32_t)zo | ((uint32_t)zpos << 16);
                 asm volatile("" : "+v"(cword));
-                if constexpr (!QUAD_EARLY_DECODE) decode_old(nxt);     // (else: decoded an iteration ago, below)
                 const bool own_new = act && lq == ln, own_old = more && lq == nxt.lo;
-                // "one lane owns both" (the rare second update below).  QUAD_SMALL: the two compare masks are ANDed HERE, next to the
-                // compares, and the branch tests the scalar result -- made at the branch, behind the basic blocks of the row conversion
-                // (and through __ballot, which takes an int), the mask was rebuilt lane by lane on the vector unit
-                uint64_t both_w = 0;
-                if constexpr (QUAD_SMALL) both_w = __builtin_amdgcn_ballot_w64(own_new) & __builtin_amdgcn_ballot_w64(own_old);
+                // "one lane owns both" (the rare second update below), ANDed HERE: made at the branch, the mask is rebuilt on the vector unit
+                const uint64_t both_w = __builtin_amdgcn_ballot_w64(own_new) & __builtin_amdgcn_ballot_w64(own_old);
                 const int sg = own_new ? sn : own_old ? nxt.so : 0;
                 const int ps = own_new ? zpos : own_old ? nxt.zo : (lq << 3);
                 const int df = own_new ? f : own_old ? -nxt.f : 0;
@@ -752,25 +672,19 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 QP_MARK(3);                                            // decode, the update's LDS reads issued
                 LLDA_MARK("scalars");
                 __builtin_amdgcn_s_setprio(QP_BULK);
-                int w_next;                                            // word of site n+2 (loaded an iteration ago)
+                // word and z of site n+2 came an iteration ago; those of site n+3 go into THIS site's set, which is done with them (the
+                // commit word is made above) and is the next iteration's prv: nothing to move when the sets rotate
+                int w_next;                                            // word of site n+2
                 if constexpr (REC) {
                     prv.v = w_next = pv; prv.f = pf; prv.c = pc;       // the record of site n+2
-                    if constexpr (QUAD_EARLY_DECODE) cur.zo = gload_i32(z_b, off(n + 3));     // (prv.zo: an iteration ago)
-                    else prv.zo = gload_i32(z_b, off(n + 2));
+                    cur.zo = gload_i32(z_b, off(n + 3));               // (prv.zo: an iteration ago)
                     load_rec(pv, pf, pc, off(n + 3));
-                } else if constexpr (QUAD_EARLY_DECODE) {
-                    // word and z of site n+2 came an iteration ago; those of site n+3 go into THIS site's set, which is done with
-                    // them (the commit word is made above) and is the next iteration's prv: nothing to move when the sets rotate
+                } else {
                     w_next = prv.v;
                     prv.f = gload_i32(freq_b, off(n + 2)); prv.c = gload_i32(csc_b, off(n + 2));
                     cur.v = gload_i32(word_b, off(n + 3)); cur.zo = gload_i32(z_b, off(n + 3));
-                } else {
-                    w_next = wq;
-                    load_scalars(prv, off(n + 2));                     // scalars of site n+2 (masked form: clamped)
-                    wq = gload_i32(word_b, off(n + 3));
                 }
-                // the old position of site n+2: the decode block of the next iteration only reads (lo, so)
-                if constexpr (QUAD_EARLY_DECODE) decode_old(prv);
+                decode_old(prv);                                       // the old position of site n+2: the next iteration only reads (lo, so)
                 QP_MARK(4);                                            // scalar / record loads of the sites ahead issued
                 // site n+1: its row (issued an iteration ago) -> fp32, own count out; then the row of site n+2 is issued
                 remove_own_packed(nxt.so, (more && lq == nxt.lo) ? nxt.f : 0);
@@ -783,7 +697,6 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 *cg = w;
                 const int nd = w & 0xffff, nk = k0 + nd - (int)((uint32_t)w >> 16);
                 *pa_of(cg) = tier0_factor(nd, nk, alpha32, vbeta32);
-                if constexpr (!QUAD_SMALL) both_w = __ballot(own_new && own_old);
                 if (__builtin_expect(both_w != 0, 0)) {
                     LLDA_MARK("rare_second_update");
                     if (own_new && own_old) update(nxt.so, nxt.zo, -nxt.f);
@@ -795,20 +708,11 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
                 {
                     LLDA_MARK("commit");
                     const uint32_t zoff = opaque_u32(sb + (uint32_t)n * 4u);
-                    const uint32_t word = cword;
-                    if constexpr (QUAD_SMALL) {
-                        // (the shift drops bit 31, the flag the two-document kernel keeps there; llda_sweep: positions below 2^30)
-                        const uint32_t loff = (uint32_t)cur.c << 2;
-                        if (lq == 0 && act) {                          // (plain stores: the compiler's vmcnt bookkeeping sees them)
-                            gstore_i32(z_b, zoff, zpos);
-                            gstore_i32((int32_t *)P.commit_log, loff, (int)word);
-                        }
-                    } else {
-                        const LLDA_GLOBAL uint32_t *lp = (const LLDA_GLOBAL uint32_t *)P.commit_log + (uint32_t)(cur.c & 0x7fffffff);
-                        if (lq == 0 && act) {
-                            gstore_i32(z_b, zoff, zpos);
-                            *(LLDA_GLOBAL uint32_t *)lp = word;
-                        }
+                    // (the shift drops bit 31, the flag the two-document kernel keeps there; llda_sweep: positions below 2^30)
+                    const uint32_t loff = (uint32_t)cur.c << 2;
+                    if (lq == 0 && act) {                              // (plain stores: the compiler's vmcnt bookkeeping sees them)
+                        gstore_i32(z_b, zoff, zpos);
+                        gstore_i32((int32_t *)P.commit_log, loff, (int)cword);
                     }
                 }
 #endif
@@ -819,12 +723,10 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
         // FULL iterations three at a time (the register sets rotate with n % 3, so the hand-over is at a multiple of three) while the
         // last of the three still has site n + 3 in every document; the masked form from there to the longest document
         int n = 0;
-        if constexpr (QUAD_FULL_LOOP) {
-            for (; n + 5 < minlen; n += 3) {
-                site(QuadForm<true>{}, n, R0, R1, R2);
-                site(QuadForm<true>{}, n + 1, R1, R2, R0);
-                site(QuadForm<true>{}, n + 2, R2, R0, R1);
-            }
+        for (; n + 5 < minlen; n += 3) {
+            site(QuadForm<true>{}, n, R0, R1, R2);
+            site(QuadForm<true>{}, n + 1, R1, R2, R0);
+            site(QuadForm<true>{}, n + 2, R2, R0, R1);
         }
         for (;; n += 3) {                                           // (uniform trip count: the longest document of the wavefront)
             site(QuadForm<false>{}, n, R0, R1, R2);
@@ -868,12 +770,10 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
     }
 }
 
-// ---------------------------------------------------------------------------------------------
 // llda_pack_rows16_all: the 16-bit image of EVERY row of n_kw (layouts of 16 slots per lane, G = 8, 16, 32 lanes: 2 G threads per row;
 // the 16-byte pieces of llda_pack_rows16 -- slots 8 j .. 8 j + 7 of standard lane g -- in the order the quad kernel reads them: piece
-// (j, g & 1) of quad lane g >> 1 at 16-byte unit (2 j + (g & 1)) * G / 2 + (g >> 1)) and, per row, whether all of its counts fit 16 bits THIS sweep (row16[v] = 1) -- a row that does
-// not is read from n_kw itself by the sweep.
-// ---------------------------------------------------------------------------------------------
+// (j, g & 1) of quad lane g >> 1 at 16-byte unit (2 j + (g & 1)) * G / 2 + (g >> 1)) and, per row, whether all of its counts fit 16 bits
+// THIS sweep (row16[v] = 1) -- a row that does not is read from n_kw itself by the sweep.
 template <int G>
 __global__ void __launch_bounds__(256) llda_pack_rows16_all_kernel(const int32_t *__restrict__ n_kw, uint16_t *__restrict__ out,
                                                                    uint8_t *__restrict__ row16, int64_t V)

@@ -457,7 +457,7 @@ int llda_sweep(const llda_sweep_args *a, void *stream)
     if (rc) return rc;
     const llda_layout &L = *Lp;
     SweepPlan p;
-    rc = sweep_plan(*a, L, QUAD_HOOKS_OUT, &p);
+    rc = sweep_plan(*a, L, true, &p);                   // (true: the quad kernels compile the margin hooks out of production)
     if (rc || p.family == SWEEP_NONE) return rc;
 
     KParams P;

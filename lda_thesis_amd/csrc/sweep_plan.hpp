@@ -29,7 +29,7 @@
 //       dm == -10         (0, 1 / 1.05f), margin_rel = 2^-40
 //       dm == -11 .. -18  (0, 2^(dm + 10)), margin_rel = 2^-40
 //       every other dm    base values
-//   LB = 4 / 3 / 2 for G = 32 / 16 / 8;  REC = G <= 16;  PAD = K != KP;  HOOKS = dm != 0 || !QUAD_HOOKS_OUT (kernel_quad.hpp)
+//   LB = 4 / 3 / 2 for G = 32 / 16 / 8;  REC = G <= 16;  PAD = K != KP;  HOOKS = dm != 0 || !quad_hooks_out
 //   grid = ceil(D / ((2 * 128 / G) * dpg)), 128 threads
 // Two-document 16-bit rows (n_kw16 and site_row, BAD_ARG when one comes without the other): BAD_ARG unless fast && dense && logged &&
 //   T == 16 && G >= 32 and both images 16-byte aligned;  W4 = 0 < max_doc_tokens < 65536 && dm != -8
@@ -162,7 +162,8 @@ inline int plan_sparse(const llda_sweep_args &a, SweepPlan &p)
 }
 
 // The plan of llda_sweep(&a): LLDA_OK and *out, or the refusal.  a.D >= 0 and a.V >= 1 (llda_sweep checks them before it asks for the
-// layout); L is llda_layout_init(a.K); quad_hooks_out is kernel_quad.hpp's QUAD_HOOKS_OUT (true in the production build).
+// layout); L is llda_layout_init(a.K); quad_hooks_out: production (debug_margin == 0) runs the quad kernels' instantiation with the
+// margin hooks compiled out (llda_sweep passes true).
 inline int sweep_plan(const llda_sweep_args &a, const llda_layout &L, bool quad_hooks_out, SweepPlan *out)
 {
     SweepPlan p = {};
