@@ -303,7 +303,9 @@ typedef struct llda_batch_args {
 } llda_batch_args;
 int llda_sweep_batch(const llda_batch_args *args, void *stream);
 
-/* n_kw[i] += delta[i]; delta[i] = 0  for i < n   (end-of-sweep fold, after the all-reduce of delta). */
+/* n_kw[i] += delta[i]; delta[i] = 0  for i < n   (end-of-sweep fold, after the all-reduce of delta).  Any n >= 0 and any 4-byte
+ * aligned pointers are taken; 16-byte aligned ones are folded four counts per access, and a group of four whose deltas are all zero
+ * is not written. */
 int llda_apply_delta(int32_t *counts, int32_t *delta, int64_t n, void *stream);
 
 /* Fold a commit log into word-major counts (the deferred `+= f` / `-= f` of LabeledLDA.py:109-111,123-125).
@@ -325,7 +327,8 @@ int llda_commit_log(const int64_t *item_begin, const int32_t *item_len, const in
  * caller decides per word from that static bound; hot words stay int32).  Halves the bytes of the all-reduce.
  *
  * llda_apply_rows: counts[r*KP ..] += row r (pairs decoded), row zeroed, for r < n_rows.  With n_rows = V + 1
- * and counts = the fused [n_kw | n_k] buffer, row V is the n_k delta the sweep kernels wrote. */
+ * and counts = the fused [n_kw | n_k] buffer, row V is the n_k delta the sweep kernels wrote.  counts 8-byte aligned (the two counts
+ * of a pair word are updated with one access; LLDA_E_BAD_ARG otherwise); n_rows == 0 is a no-op. */
 int llda_apply_rows(const int64_t *row_off, int32_t *rows, int64_t n_rows, int32_t K, int32_t *counts, void *stream);
 
 /* The 16-bit image of n_kw for llda_sweep_args.n_kw16 (ABI 15; K with llda_rows16_ok).  row16[v] != 0 flags the words whose
@@ -333,7 +336,7 @@ int llda_apply_rows(const int64_t *row_off, int32_t *rows, int64_t n_rows, int32
  * sampling conserves, is at most 65535 (the reference's counts, LabeledLDA.py:109-111,123-125, only move a site's frequency
  * between two topics of one word).  Call it once per sweep, after the counts of the previous sweep were folded in and before
  * the first llda_sweep; unflagged rows of n_kw16 are not written.  A flagged row with a count outside the range sets bit 2
- * of status word 0. */
+ * of status word 0 (status may be NULL: nothing is reported then).  n_kw and n_kw16 16-byte aligned (LLDA_E_BAD_ARG otherwise). */
 int llda_pack_rows16(const int32_t *n_kw, const uint8_t *row16, int64_t V, int32_t K, uint16_t *n_kw16, int32_t *status,
                      void *stream);
 

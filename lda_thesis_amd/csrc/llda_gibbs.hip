@@ -583,6 +583,7 @@ int llda_apply_rows(const int64_t *row_off, int32_t *rows, int64_t n_rows, int32
     const llda_layout &L = *Lp;
     if (n_rows == 0) return LLDA_OK;
     if (!row_off || !rows || !counts) return LLDA_E_BAD_ARG;
+    if (misaligned(7, counts, row_off)) return LLDA_E_BAD_ARG;           // (a pair word is decoded into two counts with one 8-byte access)
     const int64_t blocks = (n_rows + 3) / 4;
     if (blocks > 0x7fffffffLL) return LLDA_E_BAD_ARG;
     hipLaunchKernelGGL(llda_apply_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, row_off, rows,
@@ -613,6 +614,7 @@ int llda_pack_rows16(const int32_t *n_kw, const uint8_t *row16, int64_t V, int32
     if (!llda_rows16_ok(K)) return LLDA_E_BAD_K;
     if (V == 0) return LLDA_OK;
     if (!n_kw || !row16 || !n_kw16) return LLDA_E_BAD_ARG;
+    if (misaligned(15, n_kw16, n_kw)) return LLDA_E_BAD_ARG;
     int rc;
     const llda_layout &L = *layout_of(K, &rc);
     const int64_t blocks = (V * 2 * L.G + 255) / 256;

@@ -180,3 +180,32 @@ def test_build_info_reports_every_ablation_switch(tmp_path):
         assert bits(d) == b, d
     assert bits(*want) == 0xfff
     assert [n for i, n in enumerate(_native.BUILD_SWITCHES)] == [d[2:].split("=")[0] for d in want]
+
+
+def test_count_and_image_entry_points_validate_arguments():
+    """the refusals include/llda_gibbs.h states for the count-folding and image-packing entry points, all of them decided on the
+    host before anything touches HIP (the pointers below are never dereferenced)."""
+    from lda_thesis_amd import _native
+    L = _native.lib()
+    BAD_K, BAD_ARG = -1, -2
+    p = ctypes.c_void_p(0x1000)                                               # 16-byte aligned, never read
+    assert L.llda_pack_image(p, 6, 8, p, None) == BAD_ARG                    # n is no multiple of 4
+    assert L.llda_pack_image(p, 8, 12, p, None) == BAD_ARG                   # bits
+    assert L.llda_pack_image(p, 8, 8, ctypes.c_void_p(0x1002), None) == BAD_ARG       # img: 4-byte aligned for bits 8 ...
+    assert L.llda_pack_image(p, 8, 16, ctypes.c_void_p(0x1004), None) == BAD_ARG      # ... 8-byte for bits 16
+    assert L.llda_pack_image(ctypes.c_void_p(0x1008), 8, 8, p, None) == BAD_ARG       # n_kw: 16-byte aligned
+    assert L.llda_pack_image(p, 0, 8, p, None) == 0
+    for K in (5, 100, 392, 1100):                                             # not llda_rows16_ok
+        assert not _native.rows16_ok(K)
+        assert L.llda_pack_rows16(p, p, 4, K, p, None, None) == BAD_K
+    assert L.llda_pack_rows16(p, p, 4, 512, ctypes.c_void_p(0x1008), None, None) == BAD_ARG     # n_kw16: 16-byte aligned
+    assert L.llda_pack_rows16(p, p, 0, 512, p, None, None) == 0
+    assert _native.rows16_ok(1024) and not _native.quad_ok(1024)
+    assert L.llda_pack_rows16_all(p, 4, 1024, p, p, None) == BAD_K
+    assert L.llda_pack_rows16_all(p, 4, 250, p, p, None) == BAD_K
+    assert L.llda_commit_log(p, p, p, 4, p, p, 8, None, p, p, None, None) == BAD_ARG          # n_k without n_k_delta
+    assert L.llda_commit_log(p, p, p, 4, p, p, 8, None, p, None, p, None) == BAD_ARG
+    assert L.llda_commit_log(None, None, None, 0, None, None, 8, None, None, None, None, None) == 0
+    assert L.llda_apply_rows(p, p, 0, 8, p, None) == 0
+    assert L.llda_apply_rows(p, p, -1, 8, p, None) == BAD_ARG
+    assert L.llda_apply_rows(p, p, 4, 8, ctypes.c_void_p(0x1004), None) == BAD_ARG            # counts: 8-byte aligned

@@ -300,3 +300,49 @@ def test_doc2bow_counts_known_tokens_in_id_order():
     bow = d.doc2bow(["c", "zzz", "a", "c", "c", "d", "a", "nope"])
     assert bow == sorted([(ids["a"], 2), (ids["c"], 3), (ids["d"], 1)])
     assert d.doc2bow([]) == [] and d.doc2bow(["zzz"]) == []
+
+
+@pytest.mark.parametrize("K,G", [(100, 8), (200, 16), (512, 32), (1024, 64)])
+def test_row_image_references_are_permutations_in_the_loaders_order(K, G):
+    """tests/countref.py: the numpy statements of llda_pack_rows16 / llda_pack_rows16_all move every (lane, slot) of the group layout
+    to exactly one place of the image, and reading the image back in the order the loaders document (the R16 loader of
+    kernel_sweep.hpp, load_row16 / convert_row of kernel_quad.hpp) gives the row -- with the layout's own pos_lane / pos_slot as
+    the witness of which count sits where."""
+    import countref
+    from lda_thesis_amd.layout import group_layout
+    L = group_layout(K)
+    assert (L.G, L.T, L.KP) == (G, 16, 16 * G)
+    pos = np.arange(L.KP, dtype=np.int32)[None, :]               # a row whose counts are their own positions (all < 65536)
+    by_lane_slot = np.zeros((G, 16), dtype=np.int64)
+    by_lane_slot[L.pos_lane, L.pos_slot] = np.arange(L.KP)
+    np.testing.assert_array_equal(countref.lane_slot(pos, G)[0], by_lane_slot)
+    sentinel = np.full((1, L.KP), 0xBEEF, dtype=np.uint16)
+    img, status = countref.pack_rows16_ref(pos, np.ones(1, np.uint8), G, sentinel)
+    assert status == 0 and sorted(img[0].tolist()) == list(range(L.KP))
+    np.testing.assert_array_equal(countref.decode_rows16(img, G)[0], by_lane_slot)
+    # the R16 loader, spelled out: lane g reads the 16-byte units g and G + g; half h of register r of unit j is slot 8 j + 2 r + h
+    units = img[0].reshape(2 * G, 8)
+    for g in (0, 1, G // 2, G - 1):
+        for s in range(16):
+            assert units[(s // 8) * G + g][s % 8] == by_lane_slot[g, s]
+    img, row16 = countref.pack_rows16_all_ref(pos, G)
+    assert row16.tolist() == [1] and sorted(img[0].tolist()) == list(range(L.KP))
+    np.testing.assert_array_equal(countref.decode_quad(img, G)[0], by_lane_slot)
+    # load_row16, spelled out: quad lane lq reads the units (2 j + e) * G / 2 + lq as the slots 8 j .. 8 j + 7 of lane 2 lq + e
+    units = img[0].reshape(2 * G, 8)
+    for g in (0, 1, G // 2, G - 1):
+        for s in range(16):
+            assert units[(2 * (s // 8) + (g & 1)) * (G // 2) + (g >> 1)][s % 8] == by_lane_slot[g, s]
+    # unflagged rows stay as they were; a count outside 0 .. 65535 in a flagged row is reported, in an unflagged one it is not
+    rows = np.vstack([pos, pos])
+    rows[1, 5] = 65536
+    img, status = countref.pack_rows16_ref(rows, np.array([1, 0], np.uint8), G, np.vstack([sentinel, sentinel]))
+    assert status == 0 and (img[1] == 0xBEEF).all()
+    assert countref.pack_rows16_ref(rows, np.array([0, 1], np.uint8), G, np.vstack([sentinel, sentinel]))[1] == 4
+    assert countref.pack_rows16_all_ref(rows, G)[1].tolist() == [1, 0]
+    rows[1, 5] = -1
+    assert countref.pack_rows16_all_ref(rows, G)[1].tolist() == [1, 0]
+    np.testing.assert_array_equal(countref.pack_image_ref(np.array([[-1, 0, 255, 256], [65535, 65536, -2 ** 31, 2 ** 31 - 1]]), 8),
+                                  [[255, 0, 255, 255], [255, 255, 255, 255]])
+    np.testing.assert_array_equal(countref.pack_image_ref(np.array([[-1, 0, 255, 256], [65535, 65536, -2 ** 31, 2 ** 31 - 1]]), 16,
+                                                          col_src=[3, 2, 1, 0]), [[256, 255, 0, 65535], [65535, 65535, 65535, 65535]])
