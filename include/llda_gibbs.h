@@ -427,19 +427,31 @@ int llda_readout_theta(const int32_t *n_dk, const uint16_t *lab_mask, int64_t D,
  *     [beta_fallback: if prob.sum() == 0 (0/0 raises in the reference): prob = (n_dk+alpha)*(ph[:,v]+beta), renormalise]
  *     while prob.sum() > 1: prob /= c_loop;   draw
  * Every `thinning` sweeps n_dk / sum(n_dk) enters a running average (avg_mode 0:
- * (s-1)/s*avg + (1/s)*cur; 1: m*avg + (1-m)*cur, m = (s-1)/s), written to th (D, KP).  z (device
- * positions) and n_dk (D, KP) receive the final state (iters = 0: the prep4test start state). */
+ * (s-1)/s*avg + (1/s)*cur; 1: m*avg + (1-m)*cur, m = (s-1)/s), written to th (D, KP); th = 0 when no sweep
+ * reaches a multiple of `thinning`.  z and n_dk (D, KP) receive the final state (iters = 0: the prep4test
+ * start state).
+ * Order of the topics.  The five matrices ph, init_rows, slot_valid, n_dk and th are LANE-MAJOR: topic k sits at
+ *   pos_lane[p] * T + pos_slot[p],  p = topic_pos[k]  (llda_layout)
+ * of its row of KP = G * T entries -- NOT at p, the group-layout position the sweep's arrays use; the two orders
+ * differ whenever T >= 8 (every K above 32).  Entries that hold no topic (slot_valid = 0) are 0 in ph and init_rows
+ * and come back 0 in n_dk and th.  Only z is in group-layout positions: z[site] = topic_pos[topic].
+ * The RNG of document d is keyed by the low 32 bits of doc_ids[d] (or of doc_base + d) and by doc_stream[d] (or stream_id).
+ * An empty document (doc_off[d] == doc_off[d+1]) gets n_dk = 0 and th = 0 on every path.
+ * Refused with LLDA_E_BAD_ARG before anything touches the device: a NULL args, doc_off, word, init_idx, freq, ph,
+ * init_rows, slot_valid, z, n_dk or th; D < 0; iters < 0; thinning < 1; c_init or c_loop that is not > 1 (1, less, NaN:
+ * the division loops above would not end).  K outside 1 .. LLDA_MAX_K: LLDA_E_BAD_K.  D == 0 is a no-op.
+ * alpha < 0 or c_loop - 1 < 1e-9 are legal: every site then takes the exact pipeline, as with exact_only. */
 typedef struct llda_foldin_args {
     const int64_t *doc_off;     /* [dev] [D+1]                                                  */
     const int32_t *word;        /* [dev] [S]                                                    */
     const int32_t *init_idx;    /* [dev] [S] row of init_rows for every site                     */
     const int32_t *freq;        /* [dev] [S]                                                    */
-    const double  *ph;          /* [dev] [V*KP] loadings, word-major, device order, 0 in padding */
-    const double  *init_rows;   /* [dev] [R*KP] initial probabilities, device order             */
-    const uint8_t *slot_valid;  /* [dev] [KP] 1 where a slot holds a topic                       */
-    int32_t *z;                 /* [dev] [S] out                                                 */
-    int32_t *n_dk;              /* [dev] [D*KP] out                                              */
-    double  *th;                /* [dev] [D*KP] out                                              */
+    const double  *ph;          /* [dev] [V*KP] loadings, word-major, lane-major rows, 0 in padding */
+    const double  *init_rows;   /* [dev] [R*KP] initial probabilities, lane-major rows, 0 in padding */
+    const uint8_t *slot_valid;  /* [dev] [KP] lane-major: 1 where an entry holds a topic         */
+    int32_t *z;                 /* [dev] [S] out: group-layout positions                         */
+    int32_t *n_dk;              /* [dev] [D*KP] out, lane-major rows (n_sites > 0: zeroed by the caller) */
+    double  *th;                /* [dev] [D*KP] out, lane-major rows                             */
     int32_t *status;            /* [dev] optional: bit 0 = a site had no positive probability    */
     int64_t D;
     int64_t doc_base;           /* RNG counter word 1 of document 0                              */
@@ -455,7 +467,9 @@ typedef struct llda_foldin_args {
     int64_t n_sites;            /* doc_off[D] (ABI 11).  > 0: the initial assignments are drawn by a separate launch with
                                    one lane group per SITE (they are independent of one another, and the reference's
                                    `while prob.sum() > 1: prob /= c` can run tens of thousands of times for one site);
-                                   n_dk must then be zeroed by the caller.  0: inside the per-document launch. */
+                                   n_dk must then be zeroed by the caller, doc_off[0] must be 0 and n_sites == doc_off[D].
+                                   0: inside the per-document launch, narrow and wide layouts alike; z and n_dk are then pure
+                                   outputs (whatever they hold is ignored).  Both give the same z, n_dk and th. */
     const int64_t  *ph_base;    /* [dev] [D] optional (ABI 11): element offset of document d's loadings inside `ph` ...  */
     const uint32_t *doc_stream; /* [dev] [D] optional: ... and its RNG stream id (instead of stream_id): documents that are
                                    sampled against DIFFERENT label subsets of the same size (the nodes of one level of

@@ -431,10 +431,13 @@ def selftest_div(n, seed=1):
 
 def foldin(*, doc_off, word, init_idx, freq, ph, init_rows, slot_valid, z, n_dk, th, status, D, K, iters, thinning,
            alpha, beta, c_init, c_loop, seed, stream_id, doc_base=0, beta_fallback=False, avg_mode=0, doc_ids=None,
-           ph_base=None, doc_stream=None, exact_only=False):
+           ph_base=None, doc_stream=None, exact_only=False, n_sites=None):
+    """llda_foldin on the current torch stream.  ph, init_rows, slot_valid, n_dk and th are lane-major (layout.lm_topic_pos), z holds
+    group-layout positions.  n_sites = None: ``word.numel()`` (the initial assignments by a launch of their own, n_dk zeroed by the
+    caller); 0: drawn inside the per-document launch, z and n_dk pure outputs.  status, doc_ids, ph_base, doc_stream may be None."""
     a = LldaFoldinArgs(_ptr(doc_off), _ptr(word), _ptr(init_idx), _ptr(freq), _ptr(ph), _ptr(init_rows),
                        _ptr(slot_valid), _ptr(z), _ptr(n_dk), _ptr(th), _ptr(status), int(D), int(doc_base), int(K),
                        int(iters), int(thinning), 1 if beta_fallback else 0, int(avg_mode), 1 if exact_only else 0, float(alpha),
                        float(beta), float(c_init), float(c_loop), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                       int(stream_id) & 0xFFFFFFFF, 0, _ptr(doc_ids), int(word.numel()), _ptr(ph_base), _ptr(doc_stream))
+                       int(stream_id) & 0xFFFFFFFF, 0, _ptr(doc_ids), int(word.numel() if n_sites is None else n_sites), _ptr(ph_base), _ptr(doc_stream))
     _launch(z, lib().llda_foldin, "llda_foldin", ctypes.byref(a))

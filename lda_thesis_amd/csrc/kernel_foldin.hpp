@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) llda_foldin_kernel(const FParams P)
 
     // thinned running average of the document-topic state (LabeledLDA.py:199-211)
     auto thin = [&](const int sweep) {
-        if (sweep >= 0 && (sweep + 1) % P.thinning == 0) {
+        if (sweep >= 0 && len > 0 && (sweep + 1) % P.thinning == 0) {      // (an empty document keeps th = 0: no 0 / 0)
             const int s2 = (sweep + 1) / P.thinning;
             const double tot = (double)ntot;
             if (s2 == 1) {

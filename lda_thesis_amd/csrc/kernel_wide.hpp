@@ -1146,7 +1146,8 @@ __global__ void __launch_bounds__(64) llda_foldin_init_wide_kernel(const WFParam
     }
 }
 
-// the sweeps (the initial assignments always come from llda_foldin_init_wide_kernel)
+// the sweeps; the initial assignments come from llda_foldin_init_wide_kernel (n_sites > 0: n_dk holds their counts) or are drawn
+// here, site by site, as llda_foldin_kernel does (n_sites == 0: n_dk is a pure output)
 __global__ void __launch_bounds__(64) llda_foldin_wide_kernel(const WFParams P)
 {
     extern __shared__ double s_wide[];
@@ -1163,16 +1164,42 @@ __global__ void __launch_bounds__(64) llda_foldin_wide_kernel(const WFParams P)
         const double *ph = F.ph + (F.ph_base ? F.ph_base[d] : 0);
         int32_t *ndk_row = F.n_dk + d * KP;                     // lane-major
         double *th_row = F.th + d * KP;
+        const bool pre = F.n_sites > 0;
         for (int t = 0; t < NT; ++t) {
             const int gv = t * 64 + lane;
             for (int s = 0; s < T; ++s) {
-                s_ndk[pos_of_rt(G, T, gv, s)] = ndk_row[gv * T + s];
+                s_ndk[pos_of_rt(G, T, gv, s)] = pre ? ndk_row[gv * T + s] : 0;
                 th_row[gv * T + s] = 0.0;
             }
         }
         int ntot = 0;
         for (int n = 0; n < len; ++n) ntot += F.freq[s0 + n];
         const double c1 = F.c_loop, c1r = 1.0 / c1;
+        if (!pre) {                                         // prep4test: the statements of llda_foldin_init_wide_kernel
+            const double c0 = F.c_init, c0r = 1.0 / c0;
+            uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+            for (int n = 0; n < len; ++n) {
+                if ((n & 127) == 0) {
+                    r0 = (uint32_t)(n >> 1) + (uint32_t)lane; r1 = gdoc; r2 = stream_id; r3 = 0xFFFFFFFFu;
+                    philox4x32_10(r0, r1, r2, r3, F.key0, F.key1);
+                }
+                const int holder = (n >> 1) & 63;
+                const uint32_t ra = (uint32_t)__shfl((int)((n & 1) ? r2 : r0), holder, 64);
+                const uint32_t rb = (uint32_t)__shfl((int)((n & 1) ? r3 : r1), holder, 64);
+                const double u = ((double)(ra >> 5) * 67108864.0 + (double)(rb >> 6)) * (1.0 / 9007199254740992.0);
+                wide_load_lm(wv, F.phn + (int64_t)F.init_idx[s0 + n] * KP, W, lane);
+                wide_shrink(wv, W, lane, c0, c0r);
+                int zn = wide_draw(wv, W, u, lane);
+                if (zn < 0) {
+                    zn = 0;
+                    if (lane == 0 && F.status) atomicOr(F.status, 1);
+                }
+                if (lane == 0) {
+                    s_ndk[zn] += F.freq[s0 + n];
+                    F.z[s0 + n] = zn;
+                }
+            }
+        }
 
         for (int sweep = 0; sweep < F.iters; ++sweep) {
             uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
@@ -1221,7 +1248,7 @@ __global__ void __launch_bounds__(64) llda_foldin_wide_kernel(const WFParams P)
                 }
             }
             // thinned running average of the document-topic state (LabeledLDA.py:199-211)
-            if ((sweep + 1) % F.thinning == 0) {
+            if (len > 0 && (sweep + 1) % F.thinning == 0) {                      // (an empty document keeps th = 0: no 0 / 0)
                 const int s2 = (sweep + 1) / F.thinning;
                 const double tot = (double)ntot;
                 const double f_old = F.avg_mode == 0 ? (double)(s2 - 1) / (double)s2 : (double)(s2 - 1) / (double)s2;

@@ -1004,6 +1004,8 @@ int llda_foldin(const llda_foldin_args *a, void *stream)
     if (!a || !a->doc_off || !a->word || !a->init_idx || !a->freq || !a->ph || !a->init_rows || !a->z || !a->n_dk ||
         !a->th || !a->slot_valid || a->D < 0 || a->iters < 0 || a->thinning < 1)
         return LLDA_E_BAD_ARG;
+    // `while prob.sum() > 1: prob /= c` ends only for c > 1 (NaN refused too)
+    if (!(a->c_init > 1.0) || !(a->c_loop > 1.0)) return LLDA_E_BAD_ARG;
     int rc;
     const llda_layout *Lp = layout_of(a->K, &rc);
     if (rc) return rc;
@@ -1029,7 +1031,7 @@ int llda_foldin(const llda_foldin_args *a, void *stream)
         memset(&W, 0, sizeof W);
         W.f = P;
         fill_wide(L, W.w);
-        // (the wide path always draws the initial assignments with one wavefront per site; n_sites = 0: no site at all)
+        // (n_sites > 0: the initial assignments with one wavefront per site; 0: llda_foldin_wide_kernel draws them itself)
         int rl = allow_lds(llda_foldin_init_wide_kernel, (size_t)L.KP * 8);
         if (rl) return rl;
         if (P.n_sites > 0)

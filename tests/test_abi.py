@@ -209,3 +209,36 @@ def test_count_and_image_entry_points_validate_arguments():
     assert L.llda_apply_rows(p, p, 0, 8, p, None) == 0
     assert L.llda_apply_rows(p, p, -1, 8, p, None) == BAD_ARG
     assert L.llda_apply_rows(p, p, 4, 8, ctypes.c_void_p(0x1004), None) == BAD_ARG            # counts: 8-byte aligned
+
+
+def test_foldin_refusals_one_by_one():
+    """every refusal include/llda_gibbs.h states for llda_foldin, each with all the other arguments in order: decided on the host
+    before anything touches HIP (no call below could launch: each has its one flaw, or D == 0; the pointers are never read)."""
+    from lda_thesis_amd import _native
+    L = _native.lib()
+    BAD_K, BAD_ARG = -1, -2
+    required = ("doc_off", "word", "init_idx", "freq", "ph", "init_rows", "slot_valid", "z", "n_dk", "th")
+
+    def call(**change):
+        a = _native.LldaFoldinArgs()
+        for name in required:
+            setattr(a, name, 0x1000)
+        a.D, a.K, a.iters, a.thinning, a.c_init, a.c_loop, a.alpha, a.n_sites = 3, 8, 2, 1, 1.0005, 1.0000005, 0.1, 7
+        for k, v in change.items():
+            setattr(a, k, v)
+        return L.llda_foldin(ctypes.byref(a), None)
+
+    for name in required:
+        assert call(**{name: None}) == BAD_ARG, name
+    assert call(D=-1) == BAD_ARG
+    assert call(iters=-1) == BAD_ARG
+    assert call(thinning=0) == BAD_ARG
+    assert call(thinning=-2) == BAD_ARG
+    assert call(K=0) == BAD_K
+    assert call(K=7689) == BAD_K
+    for c in (1.0, 0.5, float("nan")):                                        # `while prob.sum() > 1: prob /= c` would not end
+        assert call(c_init=c) == BAD_ARG, c
+        assert call(c_loop=c) == BAD_ARG, c
+        assert call(c_init=c, D=0) == BAD_ARG, c
+    assert call(D=0) == 0                                                     # nothing to sample
+    assert call(D=0, status=None, doc_ids=None, ph_base=None, doc_stream=None, n_sites=0, K=7688) == 0
