@@ -20,12 +20,11 @@ Any K up to 7 688 (``layout.MAX_K``): up to 8 of numpy's pairwise-sum leaves the
 that ``layout.wide`` is set, G counts the virtual lanes of one wavefront, and ``llda_sweep`` picks the wide kernels
  -- nothing in this class differs except the ``max_doc_tokens`` hint it hands them.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import _native
+from . import sampler_plan as P
 from .layout import group_layout
 
 
@@ -64,14 +63,14 @@ class GibbsSampler(object):
     seed, stream_id, doc_base : RNG key / counter words (doc_base = global id of local doc 0).
     group    : torch.distributed process group (None = default group when initialised).
     sparse_labels : True (default) = documents that allow few topics run through the sparse kernel when it
-               fits (<= 64 allowed topics, at most a quarter of K); False forces the dense kernel.
+               fits (``sampler_plan.doc_is_heavy`` / ``shard_is_dense``); False forces the dense kernel.
     sharded  : True (default) = the local documents are one shard of a corpus spread over the ranks
                of ``group``: deltas are all-reduced every sweep.  False = a self-contained problem
                (e.g. one CascadeLDA sub-problem per GPU): no collective at all.
     commit_log : True = the sweep kernels log (old, new) topic per site in word-major order and
                ``llda_commit_log`` folds the log into n_kw without global atomics; False = int32 atomics on the
-               delta buffer from inside the sweep kernels.  Same counts either way.  None (default) = log from
-               2^20 local sites up (below that the extra pass costs more than the atomics it saves).
+               delta buffer from inside the sweep kernels.  Same counts either way.  None (default) =
+               ``sampler_plan.commit_log`` decides by the number of local sites.
     overlap_ranges : C > 1 = the local documents are cut into C contiguous ranges; the exchange rows of range i are
                all-reduced (asynchronously, on the collective's own stream) while range i+1 is still being sampled.
                Every range exchanges its own dense rows, so C ranges move C times the bytes -- see DESIGN.md section 7
@@ -84,38 +83,37 @@ class GibbsSampler(object):
                corpora with V = 300 000 / 1 000 000, + 50 % with uniform words over a 1 GB n_kw, + 13 ... 21 % at K = 1024;
                - 6 % at K = 512 with a 41 MB n_kw, all at three waves per SIMD.  Where every document holds fewer than 2^16 tokens
                the kernel packs n_dk with its sweep-start value and runs FOUR waves per SIMD: another + 7 ... 10 %, and ahead of
-               the int32 kernel at every size measured.  None (default) = where the kernel has it (dense
-               mask, commit log, K = 512 or 1024) and either every document is below 2^16 tokens or n_kw is at least
-               ROWS16_MIN_BYTES (64 MiB); True = wherever the
-               kernel has it; False = off.  The image costs V*KP*2 bytes (half of n_kw again) inside the allocation of
-               the counts plus 4 bytes per site; with rows16=None a shard that has no room for it sweeps with int32 rows
-               (with a warning) and the environment variable LLDA_ROWS16=on|off decides for callers that cannot pass the
-               argument.
+               the int32 kernel at every size measured.  None (default) = where those measurements say it
+               pays, True = wherever the kernel has it, False = off: the rule is ``sampler_plan.rows_possible`` / ``rows``.  The
+               image costs V*KP*2 bytes (half of n_kw again) inside the allocation of the counts plus 4 bytes per site; with
+               rows16=None a shard that has no room for it sweeps with int32 rows (with a warning).
     quad     : K = 512 (and every K whose layout has 16 slots per lane in 8, 16 or 32 lanes that all hold topics: 97 .. 128, most of
                185 .. 256 and 361 .. 512 -- ``_native.quad_ok``) with the 16-bit rows and every document below 2^16 tokens: the kernel
                that walks FOUR documents per wavefront (16 lanes x 32 slots each; eight / sixteen documents for the 16- / 8-lane layouts;
                csrc/kernel_quad.hpp) on an image of EVERY row -- which rows fit 16 bits is decided per
                sweep by ``llda_pack_rows16_all`` from the counts themselves; a row that does not is read as int32.  Same results.
-               None (default) = wherever it applies AND the rows that do not fit 16 bits are rare: at most QUAD_MAX_WIDE_SITES of the
-               sites may read such a row (the quad kernel reads it without prefetch) -- looked at when the sampler is built and every
-               QUAD_CHECK_EVERY sweeps from the library's own flags, without synchronising; beyond that the sampler goes over to the
-               two-document kernel with its int32 rows for good.  True = always; False = the two-documents-per-wavefront kernel;
-               LLDA_QUAD=on|off in the environment decides for callers that cannot pass the argument.
+               None (default) = wherever it applies AND the rows that do not fit 16 bits are rare (the quad kernel reads such a row
+               without prefetch) -- looked at when the sampler is built (``sampler_plan.rows``) and every QUAD_CHECK_EVERY sweeps from
+               the library's own flags, without synchronising (``sampler_plan.quad_handover``: the sampler then goes over to the
+               two-document kernel with its int32 rows for good).  True = always; False = the two-documents-per-wavefront kernel.
     image_order : the narrow image keeps its columns in an order of its own: topics that are allowed TOGETHER (label co-occurrence over
                the local documents, weighted by their sites) are packed into the same 128-byte lines by a greedy clustering, so a site's
                gathers touch fewer lines -- the sparse-label kernel is bound by the L2's line fills.  The counts, the draw order and the
-               results are untouched (``llda_pack_image_cols`` / ``llda_sweep_args.img_col``).  None (default) = taken when it saves at
-               least a tenth of the lines a site touches (``image_lines_per_site`` = (before, after)); True = always; False = never.
+               results are untouched (``llda_pack_image_cols`` / ``llda_sweep_args.img_col``).  None (default) = taken when it saves
+               enough of the lines a site touches (``image_lines_per_site`` = (before, after); ``sampler_plan.image_order_taken``);
+               True = always; False = never.
     build_lock : a context manager the heavy LOCAL sections of the construction run under (the sorts of the commit log, the count
                initialisation, the images) -- never a collective.  For several processes that share one device (bench.py --one-device,
                tests): concurrent constructions are time-sliced by the GPU's scheduler and take seconds to minutes instead of one second.
     image    : sparse label sets (the sparse-label kernel): the kernel gathers its counts from a SATURATING narrow image of n_kw
                (8 or 16 bits per count, refreshed by ``llda_pack_image`` at the start of every sweep) and re-reads an entry that
                shows 255 / 65535 from n_kw itself: a row spans a quarter / half as many cache lines, and the kernel is bound by
-               the L2's line fills.  Same results.  None (default) = 8, 16 or no image by the size of the problem (n_kw of at
-               least IMAGE_MIN_BYTES and IMAGE_MIN_SITES sites) and the share of gathers that would escape; 0 = off; 8 / 16 = that
-               image wherever the sparse-label kernel runs.  Costs V*KP (8) or 2*V*KP (16) bytes; LLDA_IMAGE=0|8|16 in the
-               environment decides for callers that cannot pass the argument.
+               the L2's line fills.  Same results.  None (default) = 8, 16 or no image by the size of the problem and the share of
+               gathers that would escape (``sampler_plan.image_bits``); 0 = off; 8 / 16 = that image wherever the sparse-label
+               kernel runs.  Costs V*KP (8) or 2*V*KP (16) bytes.
+
+    For callers that cannot pass ``rows16``, ``quad`` or ``image`` the environment decides (``sampler_plan.options``).  What was
+    decided for this shard is the named record ``plan`` (``sampler_plan.SamplerPlan``).
     """
 
     def __init__(self, doc_off, word, freq, z, K, V, alpha, beta, labs=None, counts=None, seed=0,
@@ -125,7 +123,7 @@ class GibbsSampler(object):
         _native.lib()                                       # fail loudly when the extension is missing
         _native.require_device()                            # ... or when no GPU is visible: there is no CPU fallback
         import contextlib
-        locked = build_lock if build_lock is not None else contextlib.nullcontext()
+        self._build_lock = build_lock if build_lock is not None else contextlib.nullcontext()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.K, self.V = int(K), int(V)
         self.alpha, self.beta = float(alpha), float(beta)
@@ -142,17 +140,31 @@ class GibbsSampler(object):
         self.exchange_always = bool(exchange_always)   # take the exchange path even with a single rank (tests)
         self.overlap_ranges = max(1, int(overlap_ranges))
         self.comm_events = None        # set to [] to record (start, end) event pairs around the waits for the collectives
-        self.layout = lay = group_layout(self.K)
-        dev = self.device
+        self._sort_docs = bool(sort_docs)
+        self.layout = group_layout(self.K)
+        self.plan = P.SamplerPlan()    # what sampler_plan.py decided for this shard, stage by stage
+        self._upload_corpus(doc_off, word, freq, z)
+        self._make_label_lists(labs, sparse_labels)
+        self._make_log_and_calls(commit_log)
+        self._make_counts(counts)
+        self._make_scratch()
+        self.row_off = self.rows = self._rows_list = None
+        if self.sharded and (_dist_active(self.group) or exchange_always):
+            self._make_exchange_rows()
+        opt = P.options(rows16, quad, image)
+        self._make_rows16(opt.rows16, opt.quad)
+        self._make_image(opt.image, image_order)
 
-        def as_dev(a, dtype):
-            if isinstance(a, torch.Tensor):
-                return a.to(device=dev, dtype=dtype).contiguous()
-            return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(device=dev, dtype=dtype)
+    def _as_dev(self, a, dtype):
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(device=self.device, dtype=dtype)
 
-        self.doc_off = as_dev(doc_off, torch.int64)
-        self.word = as_dev(word, torch.int32)
-        self.freq = as_dev(freq, torch.int32)
+    def _upload_corpus(self, doc_off, word, freq, z):
+        lay, dev = self.layout, self.device
+        self.doc_off = self._as_dev(doc_off, torch.int64)
+        self.word = self._as_dev(word, torch.int32)
+        self.freq = self._as_dev(freq, torch.int32)
         self.D = int(self.doc_off.shape[0] - 1)
         self.S = int(self.word.shape[0])
         if self.S:
@@ -173,10 +185,12 @@ class GibbsSampler(object):
             pre = torch.zeros((self.S + 1,), dtype=torch.int64, device=dev)
             torch.cumsum(self.freq, 0, out=pre[1:])
             self.max_doc_tokens = int(min((pre[self.doc_off[1:]] - pre[self.doc_off[:-1]]).max().item(), 2 ** 31 - 1))
+        self.plan = self.plan._replace(max_doc_tokens=self.max_doc_tokens)
         self._topic_pos = torch.from_numpy(lay.topic_pos.astype(np.int64)).to(dev)
         self._pos_topic = torch.from_numpy(lay.pos_topic.astype(np.int64)).to(dev)
-        self.z = self._topic_pos[as_dev(z, torch.int64)].to(torch.int32)
+        self.z = self._topic_pos[self._as_dev(z, torch.int64)].to(torch.int32)
 
+    def _make_label_lists(self, labs, sparse_labels):
         self.lab_mask = self._make_masks(labs)
         # every topic allowed in every document (no labs, or label sets that are all complete): the kernels skip the mask
         self.dense_mask = labs is None or (self.D > 0 and bool((self.lab_mask == self._make_masks(None)[:1]).all()))
@@ -186,22 +200,22 @@ class GibbsSampler(object):
         self.live_max = 0
         if sparse_labels and labs is not None and self.D > 0:
             self._make_live()
+
+    def _make_log_and_calls(self, commit_log):
         self.csc_pos = self.commit_log = self.site_rec = None
         self._ranges = self._make_ranges()
-        if commit_log is None:
-            commit_log = self.S >= (1 << 20)
-        if self.S >= (1 << 31):
-            commit_log = False                      # log positions are int32
-        if commit_log and self.S > 0:
-            with locked:
-                self._make_commit_log()
-        self._sort_docs = bool(sort_docs)
-        self._call_limit = min(self.MAX_CALL_SITES, self.MAX_CALL_SITES_REC) if self.site_rec is not None else self.MAX_CALL_SITES
+        log = P.commit_log(commit_log, self.S, self.layout.G, self.MAX_CALL_SITES, self.MAX_CALL_SITES_REC)
+        self.plan = self.plan._replace(**log._asdict())
+        if log.commit_log:
+            with self._build_lock:
+                self._make_commit_log(log.site_rec)
+        self._call_limit = log.call_limit
         self._off_host = self.doc_off.cpu().numpy() if (self.S > self._call_limit or len(self._ranges) > 2) else None
         self._calls = self._make_calls(self.doc_off[1:] - self.doc_off[:-1])
         self.doc_order = self._calls[0][2]       # (order of the first -- normally the only -- call)
 
-        KP = lay.KP
+    def _make_counts(self, counts):
+        dev, KP = self.device, self.layout.KP
         self.n_dk = torch.zeros((self.D, KP), dtype=torch.int32, device=dev)
         # n_kw and n_k (and their delta buffers) are two views of ONE allocation each, so that the per-sweep
         # exchange is a single all-reduce and the fold a single launch
@@ -216,61 +230,39 @@ class GibbsSampler(object):
         self.n_k_delta = self._delta[self.V * KP:]
         self.status = torch.zeros((4,), dtype=torch.int32, device=dev)   # [flags, tier-0 unsure, exact tier, -]
         if counts is None:
-            with locked:
+            with self._build_lock:
                 _native.count_init(self.doc_off, self.word, self.freq, self.z, self.D, self.K,
                                    self.n_dk, self.n_kw, self.n_k)
             if self.sharded and _dist_active(self.group):
                 import torch.distributed as dist
                 dist.all_reduce(self._counts, group=self.group)
         else:
-            self.n_dk[:, self._topic_pos] = as_dev(counts["n_d_k"], torch.int32)
-            self.n_kw[:, self._topic_pos] = as_dev(np.asarray(counts["n_k_v"]).T, torch.int32)
-            self.n_k[self._topic_pos] = as_dev(counts["n_zk"], torch.int32)
-        # wide layouts, dense or general label masks: work space that lets the sweep keep fp32 factors only in LDS
-        # (llda_sweep_args.scratch)
+            self.n_dk[:, self._topic_pos] = self._as_dev(counts["n_d_k"], torch.int32)
+            self.n_kw[:, self._topic_pos] = self._as_dev(np.asarray(counts["n_k_v"]).T, torch.int32)
+            self.n_k[self._topic_pos] = self._as_dev(counts["n_zk"], torch.int32)
+
+    def _make_scratch(self):
+        """wide layouts, dense or general label masks: work space that lets the sweep keep fp32 factors only in LDS
+        (llda_sweep_args.scratch).  Sparse label sets: the HEAVY documents of the shard go to the general wide kernel in a launch of
+        their own (_lane_parts)."""
         self._scratch = None
-        if lay.wide and (self.live_off is None or self._heavy is not None) and self.D > 0:
-            # (sparse label sets: the HEAVY documents of the shard go to the general wide kernel in a launch of their own, _lane_parts)
+        if P.scratch(self.layout.wide, self.D, self.plan.sparse, self.plan.heavy_docs):
             nbytes = _native.sweep_scratch_bytes(self.K, max(hi - lo for lo, hi, _ in self._calls))
             if nbytes:
-                self._scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        self.row_off = self.rows = self._rows_list = None
-        if self.sharded and (_dist_active(self.group) or exchange_always):
-            self._make_exchange_rows()
-        self.row16 = self.n_kw16 = self.site_row = None
-        self.quad = False
-        for var, allowed in (("LLDA_ROWS16", ("on", "off")), ("LLDA_QUAD", ("on", "off")), ("LLDA_IMAGE", ("0", "8", "16"))):
-            if os.environ.get(var) is not None and os.environ[var] not in allowed:
-                raise ValueError("%s=%r: expected one of %s" % (var, os.environ[var], ", ".join(allowed)))
-        if rows16 is None and os.environ.get("LLDA_ROWS16") in ("on", "off"):     # for callers behind the LabeledLDA front end
-            rows16 = os.environ["LLDA_ROWS16"] == "on"
-        if quad is None and os.environ.get("LLDA_QUAD") in ("on", "off"):
-            quad = os.environ["LLDA_QUAD"] == "on"
-        self._quad_wanted = quad
-        if (rows16 is not False and self.S and self.dense_mask and self.commit_log is not None
-                and (_native.rows16_ok(self.K) or (quad is not False and _native.quad_ok(self.K)))
-                and self.alpha >= 1e-6 and self.beta >= 1e-6):
-            with locked:
-                self._make_rows16(auto=rows16 is None)
-        self.n_kw_img = None
-        if image is None and os.environ.get("LLDA_IMAGE") in ("0", "8", "16"):   # for callers behind the LabeledLDA front end
-            image = int(os.environ["LLDA_IMAGE"])
-        if image not in (None, 0, 8, 16):
-            raise ValueError("image must be None (automatic), 0 (off), 8 or 16")
-        self._img_src = self._img_col = None
-        self.image_lines_per_site = None
-        if (image != 0 and self.S and self.live_off is not None and self.alpha >= 1e-6 and self.beta >= 1e-6
-                and self.V * self.beta < 2.0 ** 40):
-            self._make_image(image)
-            if self.n_kw_img is not None and image_order is not False:
-                with locked:
-                    self._make_image_order(force=image_order)
+                self._scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        self.plan = self.plan._replace(scratch=self._scratch is not None)
 
-    IMAGE_MIN_BYTES = 32 << 20       # image=None: below this n_kw (the eight L2s hold it) or below IMAGE_MIN_SITES sites the per-sweep
-    IMAGE_MIN_SITES = 1 << 20        # llda_pack_image pass costs more than the line fills it saves
-    IMAGE_MAX_ESCAPES = 0.5          # image=None: the narrowest image whose sampled escape rate stays below this (measured: with 35 % of
-                                     # the gathers escaping -- the sparse variant of configs[3] at 1 M documents -- the 8-bit image is still
-                                     # 18 % faster than the 16-bit one: the escapes go to the hot words' rows, which the L2s hold)
+    ROWS16_MIN_BYTES = P.ROWS16_MIN_BYTES
+    QUAD_MAX_WIDE_SITES = P.QUAD_MAX_WIDE_SITES
+    QUAD_CHECK_EVERY = P.QUAD_CHECK_EVERY
+    IMAGE_MIN_BYTES = P.IMAGE_MIN_BYTES
+    IMAGE_MIN_SITES = P.IMAGE_MIN_SITES
+    IMAGE_MAX_ESCAPES = P.IMAGE_MAX_ESCAPES
+    MAX_CALL_SITES = P.MAX_CALL_SITES
+    MAX_CALL_SITES_REC = P.MAX_CALL_SITES_REC
+    LOG_ITEM = P.LOG_ITEM
+    PAIR_LIMIT = P.PAIR_LIMIT
+    MAX_FREQ = P.MAX_FREQ
 
     def _image_escape_rates(self, sample=1 << 18):
         """share of the gathers of a sweep (site x allowed topic of its document) whose count would saturate an 8-bit / a 16-bit
@@ -287,36 +279,33 @@ class GibbsSampler(object):
         total = max(int(ok.sum().item()), 1)
         return (int(((x >= 255) & ok).sum().item()) / total, int(((x >= 65535) & ok).sum().item()) / total)
 
-    def _make_image(self, bits=None):
+    def _make_image(self, image, image_order):
         """the saturating narrow image of n_kw for the sparse-label kernels (llda_sweep_args.n_kw_img): uint8 / int16 [V, KP],
-        refreshed by llda_pack_image at the start of every sweep.  bits=None picks 8, 16 or no image from the size of the problem
-        and the sampled escape rates; the choice only ever changes how fast a sweep runs."""
+        refreshed by llda_pack_image at the start of every sweep, and its column order.  Whether there is one, and of 8 or 16 bits,
+        is sampler_plan.image_bits' verdict; the choice only ever changes how fast a sweep runs."""
+        self.n_kw_img = self._img_src = self._img_col = None
+        self.image_lines_per_site = None
         n = self.V * self.layout.KP
-        if self.live_max == 0:
-            return                                              # (every document is heavy: no launch of the sparse-label kernel)
         try:
-            if bits is None:
-                if n * 4 < self.IMAGE_MIN_BYTES or self.S < self.IMAGE_MIN_SITES:
-                    return
-                r8, r16 = self._image_escape_rates()
-                bits = 8 if r8 <= self.IMAGE_MAX_ESCAPES else 16 if r16 <= self.IMAGE_MAX_ESCAPES else 0
-                if not bits:
-                    return
-            self.n_kw_img = torch.zeros((n,), dtype=torch.uint8 if bits == 8 else torch.int16, device=self.device)
+            bits = P.image_bits(image, self.S, self.V, self.layout.KP, self.plan.sparse, self.live_max, self.alpha, self.beta,
+                                self._image_escape_rates, self.IMAGE_MIN_BYTES, self.IMAGE_MIN_SITES, self.IMAGE_MAX_ESCAPES)
+            if bits:
+                self.n_kw_img = torch.zeros((n,), dtype=torch.uint8 if bits == 8 else torch.int16, device=self.device)
         except torch.cuda.OutOfMemoryError:
             import warnings
             warnings.warn("GibbsSampler: no room for the narrow image of n_kw (%.1f GB at 8 bits); gathering from n_kw itself" % (n / 1e9))
-            self.n_kw_img = None
+            self.n_kw_img, bits = None, 0
+        if bits and P.image_order_possible(image_order, self.layout.KP, bits):
+            with self._build_lock:
+                self._make_image_order(image_order, P.image_cols_per_line(bits))
+        self.plan = self.plan._replace(image_bits=bits, image_order=self._img_src is not None)
 
-    def _make_image_order(self, force=None):
+    def _make_image_order(self, force, per_line):
         """column order of the narrow image: a greedy clustering of the label co-occurrence matrix into lines of 128 bytes.
         C[p, q] = sum over the local documents that allow both p and q of the document's sites (every site gathers all of its
         document's topics); a line is seeded with the heaviest position not placed yet and filled with the positions that share the
         most weight with what the line already holds.  _img_src[c] = position held by image column c, _img_col = its inverse."""
         dev, KP = self.device, self.layout.KP
-        per_line = 128 // self.n_kw_img.element_size()
-        if KP <= per_line:
-            return                                              # one line per row anyway
         lens = (self.doc_off[1:] - self.doc_off[:-1]).to(torch.float32)
         cnt = self.live_off[1:] - self.live_off[:-1]
         C = torch.zeros((KP, KP), dtype=torch.float64, device=dev)
@@ -364,13 +353,10 @@ class GibbsSampler(object):
             per_doc = torch.bincount(key // n_lines, minlength=self.D).to(torch.float32)
             return float((per_doc * lens).sum().item() / max(float(lens.sum().item()), 1.0))
         self.image_lines_per_site = (lines_per_site(pos), lines_per_site(col_t[pos]))
-        if force is not True and self.image_lines_per_site[1] > 0.9 * self.image_lines_per_site[0]:
+        if not P.image_order_taken(force, *self.image_lines_per_site):
             return
         self._img_src = torch.from_numpy(src.astype(np.int32)).to(dev)
         self._img_col = col_t.to(torch.int32)
-
-    QUAD_MAX_WIDE_SITES = 0.02       # quad=None: largest share of the sites that may read a row which does not fit the 16-bit image
-    QUAD_CHECK_EVERY = 32            # ... looked at every so many sweeps (asynchronously)
 
     def _quad_policy(self):
         """quad=None: the share of the sites whose row the library flagged as wide in THIS sweep's image, computed on the device and
@@ -386,13 +372,15 @@ class GibbsSampler(object):
         if ev is not None:
             ev.synchronize()
             self._wide_event = None
-            if float(self._wide_host[0]) > self.QUAD_MAX_WIDE_SITES * self.S:
+            target = P.quad_handover(float(self._wide_host[0]), self.S, _native.rows16_ok(self.K), self.QUAD_MAX_WIDE_SITES)
+            if target is not None:
                 self.quad = False
                 self.row16 = None
-                if _native.rows16_ok(self.K):
+                if target == "two_doc16":
                     self._flag_rows16()                # the static flags, bit 31 of csc_pos and site_row of the two-document kernel
                 else:
                     self.n_kw16 = None                 # (K = 128, 256: the int32 rows of the general kernel; the image stays allocated)
+                self.plan = self.plan._replace(rows=target)
                 return
         if self._wide_host is None:
             self._wide_host = torch.zeros((1,), dtype=torch.float32).pin_memory()
@@ -401,12 +389,7 @@ class GibbsSampler(object):
         self._wide_event = torch.cuda.Event()
         self._wide_event.record()
 
-    ROWS16_MIN_BYTES = 64 << 20      # rows16=None, documents of 2^16 tokens or more (three waves per SIMD): below this n_kw
-                                     # the L2s serve the int32 rows and the shorter kernel wins
-    MAX_FREQ = 1 << 23   # v_mad_i32_i24 moves a site's count (include/llda_gibbs.h: freq)
-    PAIR_LIMIT = 32767   # largest frequency mass of a word (all ranks) whose row is exchanged as int16 pairs
-
-    def _make_rows16(self, auto=False):
+    def _make_rows16(self, rows16, quad):
         """16-bit rows (llda_sweep_args.n_kw16): an entry of n_kw can never exceed the total of its word's row -- the
         sweep only moves a site's frequency between two topics of one word (LabeledLDA.py:109-111,123-125) and the
         exchange sums such moves --, so the rows whose total is at most 65535 (all but the few hundred most frequent
@@ -415,40 +398,41 @@ class GibbsSampler(object):
 
         The image lives in the SAME allocation as the counts, [n_kw | n_k | n_kw16]: llda_sweep_args.site_row addresses a
         row in 16-byte units from n_kw, so the distance between the two arrays is a constant of (V, KP) and never a
-        property of where the caching allocator put two tensors."""
+        property of where the caching allocator put two tensors.  Which form the rows take -- int32, the two-document
+        kernel's static flags or the quad kernel's image of every row -- is sampler_plan.rows' verdict."""
+        self.row16 = self.n_kw16 = self.site_row = None
+        self.quad = False
+        self._quad_wanted = quad
         V, KP = self.V, self.layout.KP
+        rows16_ok, quad_ok = _native.rows16_ok(self.K), _native.quad_ok(self.K)
+        if not P.rows_possible(rows16, quad, self.S, self.dense_mask, self.plan.commit_log, rows16_ok, quad_ok, self.alpha, self.beta):
+            return
+        with self._build_lock:
+            self._alloc_rows16(P.rows(rows16, quad, self.S, V, KP, rows16_ok, quad_ok, self.max_doc_tokens, self._tokens_max,
+                                      self._wide_share, lambda: bool(self._rows16_fits().any()),
+                                      self.ROWS16_MIN_BYTES, self.QUAD_MAX_WIDE_SITES))
+
+    def _tokens_max(self):
+        """(the row sums of n_dk bound every entry and never change: a site moves its count between two topics)"""
+        return int(min(int(self.n_dk.sum(dim=1, dtype=torch.int64).max().item()), 2 ** 31 - 1)) if self.D else 0
+
+    def _wide_share(self):
+        """sites whose word has a count beyond 16 bits somewhere in its row (and, for _quad_policy, the sites of every word)"""
+        wide = (self.n_kw.max(dim=1).values > 65535) | (self.n_kw.min(dim=1).values < 0)
+        self._word_sites = torch.bincount(self.word.to(torch.int64), minlength=self.V).to(torch.float32)
+        return float((wide.to(torch.float32) * self._word_sites).sum().item())
+
+    def _alloc_rows16(self, rows):
+        V, KP = self.V, self.layout.KP
+        if rows.form == "int32":
+            return
         if KP % 8:
             raise _native.NativeError("llda_rows16_ok(%d) holds but KP = %d is not a multiple of 8" % (self.K, KP))
-        # site_row is an int32: the last 16-bit row starts (V+1)*KP/4 + (V-1)*KP/8 units after n_kw
-        if (V + 1) * (KP // 4) + V * (KP // 8) >= 1 << 31:
-            if auto:
-                return
-            raise ValueError("rows16=True: n_kw of %d x %d is too large for the 32-bit row offsets of the 16-bit-row kernel"
-                             % (V, KP))
-        # (the row sums of n_dk bound every entry and never change: a site moves its count between two topics)
-        tokens_max = int(min(int(self.n_dk.sum(dim=1, dtype=torch.int64).max().item()), 2 ** 31 - 1)) if self.D else 0
-        four_waves = 0 < tokens_max < 65536
-        if auto and not four_waves and V * KP * 4 < self.ROWS16_MIN_BYTES:
-            return
-        quad = bool(self._quad_wanted is not False and four_waves and _native.quad_ok(self.K) and V < (1 << 22)
-                    and self.S < (1 << 30))      # (the quad kernel addresses the commit log with 32-bit byte offsets)
-        two_doc = _native.rows16_ok(self.K)       # the kernel with static flags (bit 31 of csc_pos, site_row): K = 512, 1024
-        if quad and self._quad_wanted is None:
-            # sites whose word has a count beyond 16 bits somewhere in its row: rare, or the two-document kernel's prefetched int32 rows
-            wide = (self.n_kw.max(dim=1).values > 65535) | (self.n_kw.min(dim=1).values < 0)
-            self._word_sites = torch.bincount(self.word.to(torch.int64), minlength=V).to(torch.float32)
-            if float((wide.to(torch.float32) * self._word_sites).sum().item()) > self.QUAD_MAX_WIDE_SITES * self.S:
-                quad = False
-        if self._quad_wanted and not quad:
-            raise ValueError("quad=True: needs a K with llda_quad_ok (16 slots per lane in 8, 16 or 32 lanes: K = 100, 128, 200, 256, 400, 512 ...), "
-                             "documents of fewer than 65 536 tokens, a vocabulary below 2^22 words and fewer than 2^30 sites")
-        if not quad and not (two_doc and bool(self._rows16_fits().any())):
-            return
         n32 = (V + 1) * KP
         try:
             both = torch.zeros((n32 + V * KP // 2,), dtype=torch.int32, device=self.device)
         except torch.cuda.OutOfMemoryError:
-            if not auto:
+            if not rows.tolerate_oom:
                 raise
             import warnings
             warnings.warn("GibbsSampler: no room for the 16-bit image of n_kw (%.1f GB); sweeping with int32 rows"
@@ -460,18 +444,15 @@ class GibbsSampler(object):
         self.n_k = self._counts[V * KP:]
         self._counts16 = both                                  # (keeps the one allocation alive under its own name)
         self.n_kw16 = both[n32:].view(torch.int16)
+        self.max_doc_tokens = rows.max_doc_tokens
+        self.plan = self.plan._replace(rows=rows.form, max_doc_tokens=rows.max_doc_tokens)
         # four documents per wavefront (llda_sweep_args.row16): K = 512, documents below 2^16 tokens; the flags are the library's,
         # rewritten every sweep
-        self.quad = quad
+        self.quad = rows.form == "quad16"
         if self.quad:
             self.row16 = torch.zeros((V,), dtype=torch.uint8, device=self.device)
-            self.max_doc_tokens = tokens_max
-            return
-        self._flag_rows16()
-        # llda_sweep_args.max_doc_tokens: below 2^16 the 16-bit-row kernel packs n_dk with its sweep-start value and runs four
-        # waves per SIMD
-        if not self.max_doc_tokens:
-            self.max_doc_tokens = tokens_max
+        else:
+            self._flag_rows16()
 
     def _rows16_fits(self):
         return (self.n_kw.sum(dim=1, dtype=torch.int64) <= 65535) & (self.n_kw.min(dim=1).values >= 0)
@@ -570,10 +551,9 @@ class GibbsSampler(object):
         return torch.where(m >= 32768, m - 65536, m).to(torch.int16).contiguous()
 
     def _make_live(self):
-        """per document the device positions of its allowed topics (draw order) for the sparse-label kernel.  A document that allows
-        more than 64 topics or more than a quarter of K is HEAVY: it keeps an empty list and is swept by the dense kernel with its
-        label mask (its own launch, _lane_parts); when more than half of the documents are heavy the whole shard takes the dense
-        kernel, as if sparse_labels were off."""
+        """per document the device positions of its allowed topics (draw order) for the sparse-label kernel.  A HEAVY document
+        (sampler_plan.doc_is_heavy) keeps an empty list and is swept by the dense kernel with its label mask (its own launch,
+        _lane_parts); a shard of mostly heavy documents takes the dense kernel altogether (sampler_plan.shard_is_dense)."""
         lay, dev = self.layout, self.device
         shifts = torch.arange(lay.T, device=dev, dtype=torch.int32)
         lm_pos = torch.from_numpy(lay.lm_pos.astype(np.int64)).to(dev)
@@ -583,7 +563,7 @@ class GibbsSampler(object):
             bits = (self.lab_mask[d0:d0 + step].to(torch.int32) & 0xFFFF)          # (chunk, G) lane masks
             allowed = ((bits.unsqueeze(-1) >> shifts) & 1).reshape(bits.shape[0], lay.KP)   # (lane, slot) order = draw order
             c = allowed.sum(dim=1)
-            h = (c > 64) | (c * 4 > self.K)
+            h = (c > P.HEAVY_TOPICS) | (c * P.HEAVY_K_PARTS > self.K)                # sampler_plan.doc_is_heavy, per document
             allowed = allowed * (~h).to(allowed.dtype)[:, None]
             _, lm = torch.nonzero(allowed, as_tuple=True)                      # row-major => draw order ascending
             counts.append(torch.where(h, torch.zeros_like(c), c))
@@ -591,7 +571,7 @@ class GibbsSampler(object):
             pos.append(lm_pos[lm])                                             # ... as memory positions
         heavy = torch.cat(heavy)
         n_heavy = int(heavy.sum().item())
-        if n_heavy * 2 > self.D:
+        if P.shard_is_dense(n_heavy, self.D):
             return                                                             # dense kernel is the better fit
         counts = torch.cat(counts)
         self.live_off = torch.zeros((self.D + 1,), dtype=torch.int64, device=dev)
@@ -601,6 +581,7 @@ class GibbsSampler(object):
             self.live_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.live_max = int(counts.max().item())
         self._heavy = heavy if n_heavy else None
+        self.plan = self.plan._replace(sparse=True, heavy_docs=n_heavy)
 
     def _make_ranges(self):
         """document bounds of the overlap ranges (contiguous, balanced by site count); one range = no overlap."""
@@ -608,10 +589,6 @@ class GibbsSampler(object):
         if C <= 1:
             return [0, self.D]
         return shard_documents(self.doc_off.cpu().numpy(), C)      # (empty ranges when D < C: every rank makes C)
-
-    LOG_ITEM = 4096    # most log entries one wavefront of llda_commit_log folds (hot words are cut into items)
-    MAX_CALL_SITES = (1 << 30) - 1   # llda_sweep addresses the sites of one call with 32-bit byte offsets
-    MAX_CALL_SITES_REC = (1 << 28) - 1   # ... and the 16-byte site records of narrow layouts
 
     def _make_calls(self, lens):
         """document ranges of the llda_sweep calls of one sweep (one range unless the shard spans 2^30 sites),
@@ -643,7 +620,7 @@ class GibbsSampler(object):
         documents are split by the lanes THEY need -- a corpus in which a few documents carry twenty labels and the rest a handful no
         longer runs all of them one to a half-wavefront -- and the HEAVY documents (_make_live) go to the dense kernel.  Which launch a
         document is in changes nothing (snapshot semantics); ``order`` is kept inside a class."""
-        if self.live_off is None or (self.live_max <= 8 and self._heavy is None) or hi <= lo:
+        if P.one_launch(self.live_off is not None, self.live_max, self._heavy is not None) or hi <= lo:
             return [(order, hi - lo, self.live_max)]
         key = (lo, hi)
         hit = self._parts_cache.get(key)
@@ -653,7 +630,7 @@ class GibbsSampler(object):
         n = (self.live_off[lo + 1:hi + 1] - self.live_off[lo:hi])[idx]
         heavy = self._heavy[lo:hi][idx] if self._heavy is not None else torch.zeros_like(n, dtype=torch.bool)
         parts = []
-        for lanes, low in ((8, -1), (16, 8), (32, 16), (64, 32)):             # (a document that allows nothing: first class, as before)
+        for lanes, low in P.LANE_CLASSES:                                     # (a document that allows nothing: first class)
             sel = idx[(n > low) & (n <= lanes) & ~heavy]
             if sel.numel():
                 parts.append((sel.to(torch.int32).contiguous(), int(sel.numel()), lanes))
@@ -663,7 +640,7 @@ class GibbsSampler(object):
         self._parts_cache[key] = (order, parts)              # (holds the keyed tensor: one entry per call range)
         return parts
 
-    def _make_commit_log(self):
+    def _make_commit_log(self, site_rec):
         """word-major (CSC) view of the sites -- range by range when the exchange is pipelined over document ranges
         -- : position of every site, frequencies in that order, and the work items of llda_commit_log (runs of at
         most LOG_ITEM entries of one word of one range)."""
@@ -698,7 +675,7 @@ class GibbsSampler(object):
         # layouts with 8 or 16 lanes per document: {word, freq, csc_pos} as one 16-byte record per site
         # (llda_sweep_args.site_rec: those kernels are bound by the number of cache lines their scalar loads touch)
         self.site_rec = None
-        if self.layout.G <= 16:
+        if site_rec:
             self.site_rec = torch.stack([self.word, self.freq, self.csc_pos, torch.zeros_like(self.word)], dim=1).contiguous()
 
     # ------------------------------------------------------------------ the hot path
@@ -729,9 +706,7 @@ class GibbsSampler(object):
             _native.pack_rows16_all(self.n_kw, self.K, self.n_kw16, self.row16)
             if self._quad_wanted is None:
                 self._quad_policy()
-        if self.quad:
-            pass
-        elif self.n_kw16 is not None:
+        if not self.quad and self.n_kw16 is not None:         # (also the sweep in which _quad_policy handed over)
             _native.pack_rows16(self.n_kw, self.row16, self.K, self.n_kw16, self.status)
         if self.n_kw_img is not None and self._img_src is not None:
             _native.pack_image_cols(self.n_kw, self.K, self._img_src, self.n_kw_img)
