@@ -237,7 +237,7 @@ int         llda_build_info(void);
 const char *llda_strerror(int code);
 int         llda_last_hip_error(void);
 /* sizeof of the argument structs as the library was compiled (0 llda_layout, 1 llda_sweep_args, 2 llda_batch_args,
- * 3 llda_foldin_args, 4 llda_rank_args, 5 llda_heldout_args): a binding checks its own struct definitions against it once, at load time. */
+ * 3 llda_foldin_args, 4 llda_rank_args, 5 llda_heldout_args, 6 llda_attr_args): a binding checks its own struct definitions against it once, at load time. */
 int         llda_struct_size(int which);
 /* Fill *out for K topics.  Mirrors numpy's pairwise-sum recursion (np.sum at LabeledLDA.py:117). */
 int         llda_layout_init(int32_t K, llda_layout *out);
@@ -601,6 +601,58 @@ typedef struct llda_heldout_args {
 } llda_heldout_args;
 #define LLDA_HELDOUT_MAX_FREQ 8388607
 int llda_heldout_loglik(const llda_heldout_args *args, void *stream);
+
+/* Credit attribution and the deterministic EM fold-in (additive to ABI 22): the E-step of the document model.
+ * With theta fixed (iters = 0) it says which share of every word belongs to which label; iterated with the matching M-step it is a
+ * fold-in without random numbers.
+ *   doc_off [D+1] int64, word [S] int32, freq [S] int32 or NULL (= all 1; 0 <= f < 2^23): the sites, a CSR;
+ *   theta [D][ld_theta] doubles: the start loads; phi_t [V][ld_phi] doubles, word-major; both row-major in REFERENCE topic order,
+ *   ld_* >= K the row strides.  Columns >= K are never read.  iters >= 0 EM steps; alpha >= 0 is read only when iters > 0.
+ * Every operation is one IEEE float64 operation, rounded on its own.  sum64(x): 64 partial sums part[j] = x[j] + x[j+64] + ... in
+ * increasing index from +0.0; then for s = 1, 2, 4, 8, 16, 32: part[j] = part[j] + part[j xor s] for every j at once; the sum is
+ * part[0] (the rule of llda_heldout_loglik).
+ *   site (w, f)  t[k] = theta[k] * phi_t[w][k];  p = sum64(t).  The site is GOOD when w is in [0, V) and LLDA_ATTR_MIN_P <= p < inf
+ *            (below 2^-960, 1/p or f/p can overflow, and 0 * inf would poison labels the document does not have).  A site that is
+ *            not good adds f to bad and nothing else (a word id outside [0, V) is never used as an index).  A good site adds f to
+ *            tok; inv = 1.0 / p (the one division per site); g = (double)f * inv; credit[k] = credit[k] + t[k] * g for every k.
+ *            The sites are added in ascending order, credit from +0.0.
+ *   step     (iters times, for a document with at least one site; a document without sites keeps its loads)
+ *            num[k] = theta[k] > 0.0 ? credit[k] + alpha : 0.0;  den = sum64(num);  0 < den < inf: theta[k] = num[k] / den for every
+ *            k, else theta stays.  Then credit, tok and bad are computed again from zero against the new loads.  A label whose load
+ *            is 0 stays 0: that is how a label set is expressed (a uniform row means "any label").
+ *   after the last step: credit is the credit against the final loads.  For a good site r[k] = t[k] * inv; the labels with
+ *            r[k] > 0, ordered by r[k] descending (the rounded r, not t), then topic id ascending; the first top_m of them go to
+ *            site_idx / site_val, padded with -1 / 0.0.  A site that is not good gets all -1 / 0.0.
+ *   theta_out [D][ld_out] doubles: the loads after iters steps (iters = 0: the bits of theta);  credit [D][ld_credit] doubles;
+ *   site_idx [S][top_m] int32 and site_val [S][top_m] double (top_m in 0 .. 4);  tok [D], bad [D] int64.  Each may be NULL on its
+ *   own; with top_m > 0 site_idx and site_val are given or left out together.  Columns >= K of the outputs are not written.
+ * A document's outputs depend on its own inputs only -- not on D, its place in the batch or the geometry -- and equal the
+ * restatement in tests/attrref.py bit for bit.  An empty document gets theta_out = theta, credit = 0, tok = bad = 0.
+ * One wavefront per document for K > 32 (theta and credit in registers up to K = 1024, in LDS beyond: 16 K bytes, one wavefront
+ * per workgroup), a group of 8, 16 or 32 >= K lanes for K <= 32.  All steps of a document run inside one launch.  The whole row of
+ * phi_t is read even where theta is 0.  D == 0 is a no-op.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args; D < 0; V outside 1 .. 2^31 - 1; an ld < K; iters < 0; alpha
+ * negative or NaN; top_m outside 0 .. 4; top_m > 0 with exactly one of site_idx / site_val NULL; a NULL doc_off, word, theta or
+ * phi_t (D > 0); a misaligned pointer.  All before anything touches HIP. */
+typedef struct llda_attr_args {
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S] or NULL                                            */
+    const double  *theta;        /* [dev] [D][ld_theta]                                          */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    int64_t  D, V, ld_theta, ld_phi, ld_out, ld_credit;
+    int32_t  K, iters, top_m, reserved;
+    double   alpha;
+    double  *theta_out;          /* [dev] [D][ld_out] or NULL                                    */
+    double  *credit;             /* [dev] [D][ld_credit] or NULL                                 */
+    int32_t *site_idx;           /* [dev] [S][top_m] or NULL                                     */
+    double  *site_val;           /* [dev] [S][top_m] or NULL                                     */
+    int64_t *tok;                /* [dev] [D] or NULL                                            */
+    int64_t *bad;                /* [dev] [D] or NULL                                            */
+} llda_attr_args;
+#define LLDA_ATTR_MIN_P 0x1p-960
+#define LLDA_ATTR_MAX_TOP 4
+int llda_attribute(const llda_attr_args *args, void *stream);
 
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds

@@ -13,6 +13,8 @@ What differs from the reference:
   * new, off by default: ``optimize_priors()`` and ``run_training(..., optimize_interval=n)`` fit alpha and beta to the counts while
     training (the reference fixes both); ``prior_trace`` records the fitted values;
   * new: ``heldout_perplexity()`` scores unseen documents by document completion on the device (``heldout.py``).
+  * new: ``word_credit()`` / ``explain()`` say which words are credited to which label, ``fold_in_em()`` / ``predict_em()`` fold unseen
+    documents in by EM, without random numbers (``attribution.py``).
 Text preparation uses ``lda_thesis_amd.text`` instead of gensim (not installable here).
 """
 import csv
@@ -439,6 +441,120 @@ class LabeledLDA(object):
         doc_off, word, freq = csr_from_doc_tups(scored)
         r = heldout.perplexity_from(*heldout.loglik(theta, ph_dev.t().contiguous(), doc_off, word, freq, weighted=weighted))
         return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped)
+
+    # ---- credit attribution and the EM fold-in (new; attribution.py) ----
+    def _attr_device(self):
+        import torch
+        return self._sampler.device if self.__dict__.get("_sampler") is not None else torch.device("cuda:%d" % torch.cuda.current_device())
+
+    def _phi_t_device(self):
+        """ph_hat (get_phi() before any thinning read-out) word-major on the device"""
+        import torch
+        dev = self._attr_device()
+        if not self.cur_perplx:
+            ph = self._sampler.phi()
+        else:
+            ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
+        if not isinstance(ph, torch.Tensor):
+            ph = torch.from_numpy(np.ascontiguousarray(ph, dtype=np.float64))
+        return ph.to(device=dev, dtype=torch.float64).t().contiguous()
+
+    def word_credit(self, top_m=1):
+        """Credit attribution on the training corpus: for every site of every document its top_m <= 4 best labels with the word's
+        posterior share per label, theta_k phi_k[w] / sum, against ``th_hat`` and ``ph_hat`` (``get_theta()`` and ``get_phi()`` before
+        any thinning read-out).  Returns dict(labels=[(len(doc), top_m) int32 arrays, -1 = padding], shares=[(len(doc), top_m) float64
+        arrays], credit=(D, K) float64: the tokens credited to every label).  th_hat is 0 outside a document's labels, so nothing is
+        credited there.  One llda_attribute launch with no EM step.  COLLECTIVE with several ranks (it reads th_hat)."""
+        import torch
+        from . import attribution
+        if not 1 <= int(top_m) <= attribution.MAX_TOP:
+            raise ValueError("top_m must be in 1 .. %d" % attribution.MAX_TOP)
+        dev = self._attr_device()
+        phi_t = self._phi_t_device()
+        if not self.cur_perplx:
+            th = self.get_theta()
+        elif self._th_hat.dev is not None and _world_size() == 1:
+            th = self._th_hat.dev
+        else:
+            th = self.th_hat
+        if not isinstance(th, torch.Tensor):
+            th = torch.from_numpy(np.ascontiguousarray(th, dtype=np.float64))
+        doc_off, word, freq = csr_from_doc_tups(self.doc_tups)
+        r = attribution.attribute(th.to(dev), phi_t, doc_off, word, freq, iters=0, top_m=top_m, want=("credit", "sites"))
+        idx, val = attribution.spans(doc_off, r["site_idx"].cpu().numpy(), r["site_val"].cpu().numpy())
+        return dict(labels=idx, shares=val, credit=r["credit"].cpu().numpy())
+
+    @staticmethod
+    def _check_tups(tups):
+        """a document with no in-vocabulary word raises, as in ``run_test``"""
+        for t in tups:
+            if not t:
+                raise ValueError("not enough values to unpack: a document has no in-vocabulary word")
+
+    def _em_start(self, tups, labels):
+        from . import attribution
+        self._check_tups(tups)
+        cols = None if labels is None else attribution.explain_label_cols(self.labelmap, len(tups), labels=labels)
+        return attribution.uniform_start(cols, len(tups), self.K)
+
+    def _fold_in_em_device(self, tups, start, iters, top_m=0, want=("theta",), phi_t=None):
+        """``iters`` EM steps from the rows ``start`` (numpy (D, K)); phi_t: ``_phi_t_device()`` where the caller has it already"""
+        import torch
+        from . import attribution
+        doc_off, word, freq = csr_from_doc_tups(tups)
+        th0 = torch.from_numpy(start).to(self._attr_device())
+        return attribution.attribute(th0, self._phi_t_device() if phi_t is None else phi_t, doc_off, word, freq, iters=iters, alpha=float(self.alpha),
+                                     top_m=top_m, want=want)
+
+    def fold_in_em(self, newdocs, iters=50, labels=None):
+        """Fold unseen documents in by EM: (D, K) float64 loads after ``iters`` steps of theta_k = (credit_k + alpha) / sum from the
+        uniform start over all K labels, or -- with ``labels``, one list of label strings per document -- over 'root' plus the
+        document's labels.  No random numbers: the same document gets the same loads on every call.  A document with no
+        in-vocabulary word raises, as in ``run_test``.  The documents are independent: no collective."""
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        start = self._em_start(tups, labels)
+        if not tups:
+            return start
+        return self._fold_in_em_device(tups, start, iters)["theta"].cpu().numpy()
+
+    def predict_em(self, newdocs, iters=50, n=5):
+        """``predict`` on the loads of ``fold_in_em``: the n <= 16 best (label, load) pairs of every document, ranked on the device."""
+        from . import ranking
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        if not tups:
+            return []
+        th = self._fold_in_em_device(tups, self._em_start(tups, None), iters)["theta"]
+        r = ranking.rank_labels(th, None, first=0, top_n=n).host()
+        names = np.array(list(self.labelmap.keys()))
+        m = min(n, self.K)
+        return [list(zip(names[idx[:m]], val[:m])) for idx, val in zip(r["top_idx"], r["top_val"])]
+
+    def explain(self, newdocs, labels=None, iters=50, n=3):
+        """Why a label: for every unseen document ([(token, f, [(label, share), ...])], {label: credited tokens}).  The label set is
+        'root' plus the given ``labels`` (one list of label strings per document) or 'root' plus the n <= 3 best non-root labels of
+        ``predict_em``; the loads are fitted on that set (``iters`` EM steps from its uniform start) and every word is attributed
+        against them with its min(4, set size) best labels, shares descending.  With at most four labels in the set a word's shares
+        sum to 1."""
+        from . import attribution, ranking
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        D = len(tups)
+        if labels is None and not 1 <= int(n) <= 3:
+            raise ValueError("n must be in 1 .. 3 (at most four labels per site: root and three)")
+        if D == 0:
+            return []
+        self._check_tups(tups)
+        phi_t = self._phi_t_device()
+        if labels is not None:
+            cols = attribution.explain_label_cols(self.labelmap, D, labels=labels)
+        else:
+            th = self._fold_in_em_device(tups, attribution.uniform_start(None, D, self.K), iters, phi_t=phi_t)["theta"]
+            ranked = ranking.rank_labels(th, None, first=1, top_n=n).host()["top_idx"]
+            cols = attribution.explain_label_cols(self.labelmap, D, ranked=ranked, n=n)
+        top_m = min(attribution.MAX_TOP, max(len(c) for c in cols))
+        r = self._fold_in_em_device(tups, attribution.uniform_start(cols, D, self.K), iters, top_m=top_m, want=("credit", "sites"),
+                                    phi_t=phi_t)
+        return attribution.explanations(tups, r["site_idx"].cpu().numpy(), r["site_val"].cpu().numpy(), r["credit"].cpu().numpy(),
+                                        list(self.labelmap.keys()), self.v_to_w)
 
     # ---- pickling: pull the device state to the host (evaluate_LabeledLDA.py:142-145 pickles the model)
     def __getstate__(self):

@@ -82,12 +82,20 @@ class LldaHeldoutArgs(ctypes.Structure):
                 ("tok", _c_p), ("bad", _c_p)]
 
 
+class LldaAttrArgs(ctypes.Structure):
+    """struct llda_attr_args (include/llda_gibbs.h)."""
+    _fields_ = [("doc_off", _c_p), ("word", _c_p), ("freq", _c_p), ("theta", _c_p), ("phi_t", _c_p), ("D", _c_i64), ("V", _c_i64),
+                ("ld_theta", _c_i64), ("ld_phi", _c_i64), ("ld_out", _c_i64), ("ld_credit", _c_i64), ("K", _c_i32), ("iters", _c_i32),
+                ("top_m", _c_i32), ("reserved", _c_i32), ("alpha", _c_d), ("theta_out", _c_p), ("credit", _c_p), ("site_idx", _c_p),
+                ("site_val", _c_p), ("tok", _c_p), ("bad", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
            "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
-           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik")
+           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik", "llda_attribute")
 
 _LIB = None
 
@@ -167,13 +175,16 @@ def lib():
     L.llda_word_cooc.argtypes = [_c_p, _c_p, _c_i64, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]
     L.llda_heldout_loglik.restype = ctypes.c_int
     L.llda_heldout_loglik.argtypes = [ctypes.POINTER(LldaHeldoutArgs), _c_p]
+    L.llda_attribute.restype = ctypes.c_int
+    L.llda_attribute.argtypes = [ctypes.POINTER(LldaAttrArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
         raise NativeError("libllda_gibbs.so ABI %d != binding ABI %d" % (L.llda_abi_version(), ABI_VERSION))
     L.llda_struct_size.restype = ctypes.c_int
     L.llda_struct_size.argtypes = [ctypes.c_int]
-    for which, struct in enumerate((LldaLayout, LldaSweepArgs, LldaBatchArgs, LldaFoldinArgs, LldaRankArgs, LldaHeldoutArgs)):
+    for which, struct in enumerate((LldaLayout, LldaSweepArgs, LldaBatchArgs, LldaFoldinArgs, LldaRankArgs, LldaHeldoutArgs,
+                                    LldaAttrArgs)):
         if L.llda_struct_size(which) != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (struct.__name__, ctypes.sizeof(struct),
                                                                            L.llda_struct_size(which)))
@@ -395,6 +406,24 @@ def heldout_loglik(doc_off, word, freq, theta, phi_t, D, V, K, *, ld_theta=None,
                         int(theta.stride(0) if ld_theta is None else ld_theta), int(phi_t.stride(0) if ld_phi is None else ld_phi),
                         int(K), 0, _ptr(mant), _ptr(expo), _ptr(tok), _ptr(bad))
     _launch(theta, lib().llda_heldout_loglik, "llda_heldout_loglik", ctypes.byref(a))
+
+
+ATTR_MIN_P = 2.0 ** -960       # LLDA_ATTR_MIN_P: a site whose p is below it (or not finite) is not attributed
+ATTR_MAX_TOP = 4               # LLDA_ATTR_MAX_TOP
+
+
+def attribute(doc_off, word, freq, theta, phi_t, D, V, K, *, iters=0, alpha=0.0, top_m=0, ld_theta=None, ld_phi=None, ld_out=None,
+              ld_credit=None, theta_out=None, credit=None, site_idx=None, site_val=None, tok=None, bad=None):
+    """llda_attribute on the current torch stream: the CSR and the two matrices as heldout_loglik takes them; iters EM steps with
+    alpha; theta_out (D, ld_out) and credit (D, ld_credit) float64, site_idx (S, top_m) int32, site_val (S, top_m) float64, tok, bad
+    (int64 [D]) the outputs, each may be None."""
+    a = LldaAttrArgs(_ptr(doc_off), _ptr(word), _ptr(freq), _ptr(theta), _ptr(phi_t), int(D), int(V),
+                     int(theta.stride(0) if ld_theta is None else ld_theta), int(phi_t.stride(0) if ld_phi is None else ld_phi),
+                     int(K if theta_out is None else theta_out.stride(0)) if ld_out is None else int(ld_out),
+                     int(K if credit is None else credit.stride(0)) if ld_credit is None else int(ld_credit),
+                     int(K), int(iters), int(top_m), 0, float(alpha), _ptr(theta_out), _ptr(credit), _ptr(site_idx), _ptr(site_val),
+                     _ptr(tok), _ptr(bad))
+    _launch(theta, lib().llda_attribute, "llda_attribute", ctypes.byref(a))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

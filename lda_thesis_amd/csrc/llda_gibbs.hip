@@ -42,6 +42,7 @@
 //   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
 //   kernel_heldout.hpp  llda_heldout_wave_kernel, _wide_kernel, _group_kernel   per-document likelihood of held-out sites as (mantissa, exponent)
+//   kernel_attr.hpp     llda_attr_wave_kernel, _lds_kernel, _group_kernel           per-word label shares, credit and the EM fold-in
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -73,6 +74,7 @@
 #include "kernel_topwords.hpp"
 #include "kernel_cooc.hpp"
 #include "kernel_heldout.hpp"
+#include "kernel_attr.hpp"
 
 namespace {
 
@@ -350,6 +352,37 @@ void fill_schedule(const llda_layout &L, int32_t &last_leaf, int32_t &tail, int3
     }
 }
 
+// llda_attribute: the kernel form by K (kernel_attr.hpp); SITES: the per-site outputs are wanted
+template <bool SITES>
+int launch_attr(const AttrParams &P, hipStream_t st)
+{
+    const int K = P.K;
+    const dim3 block(64 * ATTR_WAVES);
+    if (K <= 32) {
+        const int G = K <= 8 ? 8 : K <= 16 ? 16 : 32, docs = 64 * ATTR_WAVES / G;
+        const int64_t n_tiles = (P.D + docs - 1) / docs;
+        const dim3 grid((unsigned)(n_tiles < (1 << 20) ? n_tiles : (1 << 20)));
+        if (G == 8) hipLaunchKernelGGL((llda_attr_group_kernel<8, SITES>), grid, block, 0, st, P, n_tiles);
+        else if (G == 16) hipLaunchKernelGGL((llda_attr_group_kernel<16, SITES>), grid, block, 0, st, P, n_tiles);
+        else hipLaunchKernelGGL((llda_attr_group_kernel<32, SITES>), grid, block, 0, st, P, n_tiles);
+    } else if (K <= 1024) {
+        const int64_t blocks = (P.D + ATTR_WAVES - 1) / ATTR_WAVES;
+        const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));
+        if (K <= 64) hipLaunchKernelGGL((llda_attr_wave_kernel<1, 4, SITES>), grid, block, 0, st, P);
+        else if (K <= 128) hipLaunchKernelGGL((llda_attr_wave_kernel<2, 4, SITES>), grid, block, 0, st, P);
+        else if (K <= 256) hipLaunchKernelGGL((llda_attr_wave_kernel<4, 2, SITES>), grid, block, 0, st, P);
+        else if (K <= 512) hipLaunchKernelGGL((llda_attr_wave_kernel<8, 2, SITES>), grid, block, 0, st, P);
+        else hipLaunchKernelGGL((llda_attr_wave_kernel<16, 1, SITES>), grid, block, 0, st, P);
+    } else {
+        const size_t lds = (size_t)2 * K * sizeof(double);                   // theta and credit: at most 123 008 bytes
+        const int rl = allow_lds(llda_attr_lds_kernel<SITES>, lds);
+        if (rl) return rl;
+        const dim3 grid((unsigned)(P.D < (1 << 16) ? P.D : (1 << 16)));
+        hipLaunchKernelGGL(llda_attr_lds_kernel<SITES>, grid, dim3(64), lds, st, P);
+    }
+    return launched();
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,6 +402,7 @@ int llda_struct_size(int which)
     case 3: return (int)sizeof(llda_foldin_args);
     case 4: return (int)sizeof(llda_rank_args);
     case 5: return (int)sizeof(llda_heldout_args);
+    case 6: return (int)sizeof(llda_attr_args);
     default: return -1;
     }
 }
@@ -913,6 +947,31 @@ int llda_heldout_loglik(const llda_heldout_args *a, void *stream)
         else hipLaunchKernelGGL(llda_heldout_wide_kernel, grid, block, 0, st, P);
     }
     return launched();
+}
+
+int llda_attribute(const llda_attr_args *a, void *stream)
+{
+    if (!a) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->ld_theta < a->K || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if ((a->theta_out && a->ld_out < a->K) || (a->credit && a->ld_credit < a->K)) return LLDA_E_BAD_ARG;
+    if (a->iters < 0 || !(a->alpha >= 0.0) || a->top_m < 0 || a->top_m > LLDA_ATTR_MAX_TOP) return LLDA_E_BAD_ARG;
+    if (a->top_m > 0 && !a->site_idx != !a->site_val) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->theta || !a->phi_t) return LLDA_E_BAD_ARG;
+    if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if ((a->theta_out && a->D > INT64_MAX / a->ld_out) || (a->credit && a->D > INT64_MAX / a->ld_credit)) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->theta, a->phi_t, a->theta_out, a->credit, a->site_val, a->tok, a->bad)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->word, a->freq, a->site_idx)) return LLDA_E_BAD_ARG;
+    AttrParams P;
+    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.theta = a->theta; P.phi_t = a->phi_t;
+    P.D = a->D; P.V = a->V; P.ld_theta = a->ld_theta; P.ld_phi = a->ld_phi; P.ld_out = a->ld_out; P.ld_credit = a->ld_credit;
+    P.K = a->K; P.iters = a->iters; P.alpha = a->alpha;
+    P.theta_out = a->theta_out; P.credit = a->credit; P.tok = a->tok; P.bad = a->bad;
+    const bool sites = a->top_m > 0 && a->site_idx;                          // (top_m = 0 or no buffers: nothing in the site loop)
+    P.top_m = sites ? a->top_m : 0; P.site_idx = sites ? a->site_idx : nullptr; P.site_val = sites ? a->site_val : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    return sites ? launch_attr<true>(P, st) : launch_attr<false>(P, st);
 }
 
 int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab_mask, const int32_t *n_dk,

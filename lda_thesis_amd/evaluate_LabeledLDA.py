@@ -31,7 +31,46 @@ def build_parser():
     p.add_option("--heldout-perplexity", action="store_true", dest="heldout_perplexity", default=False,
                  help="after the report: perplexity of the held-out documents by document completion (every second word of a "
                       "document folded in, the others scored on the GPU: llda_heldout_loglik)")
+    p.add_option("--em-foldin", dest="em_foldin", type="int", default=0, metavar="ITERS",
+                 help="after the report: the same four metrics for the loads of the deterministic EM fold-in with ITERS steps "
+                      "(llda_attribute), ranked and scored on the GPU")
+    p.add_option("--explain", dest="explain", type="int", default=0, metavar="N",
+                 help="after the report: for the first N test documents the suggested labels with the five most-credited words "
+                      "of each (llda_attribute)")
     return p
+
+
+def report_em_foldin(model, test, iters):
+    """the four metrics of the report for the EM loads of the test documents (LabeledLDA.fold_in_em), through ranking.metrics"""
+    from . import ranking
+    known = set(model.vocab)
+    th = model.fold_in_em([[x for x in doc if x in known] for doc in test[0]], iters=iters)
+    m = ranking.metrics(ranking.rank_labels(th, binary_yreal(test[1], model.labelmap), first=1, top_n=0))
+    print("-----------------------------------")
+    print("EM fold-in, %d steps (no random numbers):" % iters)
+    print("AUC ROC:                 ", m["auc"])
+    print("one error:               ", m["one_error"])
+    print("two error:               ", m["two_error"])
+    print("F1 score (macro average) ", m["f1"])
+    return m
+
+
+def report_explain(model, test, n_docs, iters):
+    """for the first n_docs test documents: the suggested labels (LabeledLDA.explain) with the five most-credited words of each"""
+    known = set(model.vocab)
+    docs = [[x for x in doc if x in known] for doc in test[0][:n_docs]]
+    print("-----------------------------------")
+    print("Credit attribution of the first %d test documents:" % len(docs))
+    for d, (words, credit) in enumerate(model.explain(docs, iters=iters)):
+        print("document %d: %d tokens" % (d, sum(f for _, f, _ in words)))
+        for label in sorted(credit, key=lambda x: (-credit[x], x)):
+            got = {}
+            for token, f, shares in words:
+                for lab, share in shares:
+                    if lab == label:
+                        got[token] = got.get(token, 0.0) + f * share
+            best = sorted(got, key=lambda t: (-got[t], t))[:5]
+            print("  %-24s %8.2f  %s" % (label, credit[label], " ".join(best)))
 
 
 def report_heldout(model, test, it, thinning):
@@ -109,6 +148,10 @@ def main(argv=None):
         report_coherence(model, opt.coherence)
     if opt.heldout_perplexity:
         report_heldout(model, test, opt.it, opt.thinning)
+    if opt.em_foldin:
+        report_em_foldin(model, test, opt.em_foldin)
+    if opt.explain:
+        report_explain(model, test, opt.explain, opt.em_foldin or 50)
 
 
 if __name__ == "__main__":
