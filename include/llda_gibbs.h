@@ -440,7 +440,13 @@ int llda_readout_theta(const int32_t *n_dk, const uint16_t *lab_mask, int64_t D,
  * Refused with LLDA_E_BAD_ARG before anything touches the device: a NULL args, doc_off, word, init_idx, freq, ph,
  * init_rows, slot_valid, z, n_dk or th; D < 0; iters < 0; thinning < 1; c_init or c_loop that is not > 1 (1, less, NaN:
  * the division loops above would not end).  K outside 1 .. LLDA_MAX_K: LLDA_E_BAD_K.  D == 0 is a no-op.
- * alpha < 0 or c_loop - 1 < 1e-9 are legal: every site then takes the exact pipeline, as with exact_only. */
+ * alpha < 0 or c_loop - 1 < 1e-9 are legal: every site then takes the exact pipeline, as with exact_only.
+ * Domain of the loadings.  ph holds doubles >= 0 of ANY magnitude, init_rows probabilities.  z, n_dk and th are numpy's for every
+ * site whose products (n_dk + alpha) * ph[k][v] and whose sum S of them are finite and S > 0 -- from a subnormal S (products that
+ * underflow gradually, as numpy's do) up to the overflow threshold: a site with S < 2^-960 is never decided from prefix sums, and
+ * outside 2^-500 <= S <= 2^500 the products are multiplied by an exact power of two before they are summed and divided, so the
+ * quotients are those of numpy's true division.  What cannot equal numpy: a product or a sum that overflows (inf / inf = NaN in the
+ * reference, whose draw raises) and S == 0 without beta_fallback (0 / 0) -- both set bit 0 of status. */
 typedef struct llda_foldin_args {
     const int64_t *doc_off;     /* [dev] [D+1]                                                  */
     const int32_t *word;        /* [dev] [S]                                                    */

@@ -40,6 +40,31 @@ struct FParams {
     const uint32_t *doc_stream;   // optional [D]: ... and its RNG stream id) -- documents of different calls in one launch
 };
 
+// The range of a site's total score S = sum_k (n_dk + alpha) * ph[k][v]; the interface puts no range on ph (include/llda_gibbs.h).
+//   * The decided tier needs total >= 2^-960.  Its argument is one of RELATIVE errors: u is 0 or >= 2^-53, so above the floor
+//     u * total is 0 or >= 2^-1013, a normal double rounded to 2^-53 of itself, and the band total * 2^-40 >= 2^-1000 is exact; a
+//     score that underflowed is the double the reference's own product gives, and prefixes of subnormals add without rounding.
+//     Below 2^-969 u * total can be subnormal, rounded to the GRID of 2^-1074 -- with a total of 2^-1066 that is 2^-8 of the total,
+//     wider than any band, and the band itself underflows to 0, where `margin < total` still held: such a site was decided, and
+//     wrongly (tests/foldinties.py: 35 of 2 055 modelled sites at totals of 2^-1069 .. 2^-1062).  2^-960 is the floor the attribution
+//     and held-out kernels state, with 2^9 to spare.
+//   * The exact pipeline divides by S through y = RN(1 / S) and two exact residuals (div_by): y is inf for S < 2^-1024 and subnormal
+//     for S > 2^1022, and a residual a - S * q is exact only while its last bit, ulp(S) * ulp(q), is a double, i.e. for products a of
+//     about 2^-969 and more -- with S = 2^-1000 no product is, every quotient is rounded twice, and a last-bit tie of the draw went
+//     the other way (K = 2100, tests/test_gpu_foldin_ties.py).  So outside 2^-500 <= S <= 2^500 the PRODUCTS w are multiplied by the
+//     power of two that puts S into [1/2, 1) before the sum and the division: the products keep the roundings (gradual underflow) of
+//     numpy's a * b, a power of two changes no significand and no rounding of the sum, and w / S are the same real numbers, now
+//     divided where div_by is exact.  Inside the band nothing changes.
+constexpr double FOLDIN_TOTAL_FLOOR = 0x1p-960;
+// 0 inside the band (and for S = 0, inf, NaN: nothing to rescue, the draw reports them), else e with S * 2^-e in [1/2, 1)
+__device__ __forceinline__ int foldin_rescale_exp(double S)
+{
+    if ((S >= 0x1p-500 && S <= 0x1p500) || !(S > 0.0) || !(S < __builtin_huge_val())) return 0;
+    int e;
+    (void)frexp(S, &e);
+    return e;
+}
+
 template <int T>
 __device__ __forceinline__ void load_row_f64(const double *__restrict__ p, double (&x)[T])
 {
@@ -184,8 +209,8 @@ __global__ void __launch_bounds__(256) llda_foldin_kernel(const FParams P)
         // so that is at most ONE division -- and draws by inverse CDF; all of it is a common positive scale on every score
         // plus a few roundings (relative 2^-51 at most), so WHICH topic is drawn is decided by the signs of
         // prefix - u * total of the UNNORMALISED scores wherever those differences exceed 2^-40 of the total.  A site with
-        // a difference inside that band, a zero / non-finite total or no hit takes the reference's pipeline below -- the
-        // topic is the reference's either way; the per-site cost drops from ~600 dependent fp64 instructions (numpy-ordered
+        // a difference inside that band, a total below FOLDIN_TOTAL_FLOOR (zero included) or not finite, or no hit takes the
+        // reference's pipeline below -- the topic is the reference's either way; the per-site cost drops from ~600 dependent fp64 instructions (numpy-ordered
         // sum, IEEE divisions, second sum, scan) to ~60, and this kernel is one dependent chain per document.
         if (!P.exact_only) {
             double q[T];
@@ -228,7 +253,7 @@ __global__ void __launch_bounds__(256) llda_foldin_kernel(const FParams P)
             const uint32_t fm = pm & (0xFFFFu << cnt_lo);
             const int gbase = lane & ~(G - 1);
             const uint64_t gmask = (G == 64) ? ~0ull : ((1ull << (G & 63)) - 1ull);
-            const bool unsure = (cnt_lo != cnt_hi) || !(tot > 0.0) || !(margin < tot) || !(tot < 1.0e300);
+            const bool unsure = (cnt_lo != cnt_hi) || !(tot >= FOLDIN_TOTAL_FLOOR) || !(tot < 1.0e300);
             const uint64_t gu = (__ballot(unsure) >> gbase) & gmask, gf = (__ballot(fm != 0) >> gbase) & gmask;
             if (gu == 0 && gf != 0) {
                 const int sl = (int)__ffsll((unsigned long long)gf) - 1;
@@ -247,6 +272,11 @@ __global__ void __launch_bounds__(256) llda_foldin_kernel(const FParams P)
                 const bool real = P.slot_valid[lig * T + s] != 0;
                 w[s] = real ? ((double)ndk[s] + P.alpha) * (b[s] + P.beta) : 0.0;
             }
+            S = group_sum<G, T, HAS_TAIL>(w, K, lig, lane);
+        }
+        if (const int e = foldin_rescale_exp(S)) {          // (rare; group-uniform like S)
+#pragma unroll
+            for (int s = 0; s < T; ++s) w[s] = ldexp(w[s], -e);
             S = group_sum<G, T, HAS_TAIL>(w, K, lig, lane);
         }
         const double y = 1.0 / S;

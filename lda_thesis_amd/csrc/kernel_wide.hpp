@@ -1101,6 +1101,16 @@ __device__ __forceinline__ void wide_shrink(double *wv, const WideLayout &W, int
     }
 }
 
+// wv[i] = wv[i] * 2^k for the entries this lane owns (wide_div's chunks)
+__device__ __forceinline__ void wide_ldexp(double *wv, const WideLayout &W, int lane, int k)
+{
+    for (int q = lane; q < (W.KP >> 2); q += 64) {
+        double *p = wv + (q << 2);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = ldexp(p[j], k);
+    }
+}
+
 // wv (position order) <- row of a lane-major matrix
 __device__ __forceinline__ void wide_load_lm(double *wv, const double *row, const WideLayout &W, int lane)
 {
@@ -1233,6 +1243,10 @@ __global__ void __launch_bounds__(64) llda_foldin_wide_kernel(const WFParams P)
                             wv[pos] = real ? ((double)s_ndk[pos] + F.alpha) * (brow[gv * T + s] + F.beta) : 0.0;
                         }
                     }
+                    S = wide_sum(wv, W, lane);
+                }
+                if (const int e = foldin_rescale_exp(S)) {  // S outside 2^-500 .. 2^500: see kernel_foldin.hpp
+                    wide_ldexp(wv, W, lane, -e);
                     S = wide_sum(wv, W, lane);
                 }
                 wide_div(wv, W, lane, S, 1.0 / S);                               // prob /= prob.sum()
