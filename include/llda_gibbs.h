@@ -660,6 +660,70 @@ typedef struct llda_attr_args {
 #define LLDA_ATTR_MAX_TOP 4
 int llda_attribute(const llda_attr_args *args, void *stream);
 
+/* Left-to-right estimate of a document's likelihood p(w_d | phi, alpha) (additive to ABI 22): Wallach, Murray, Salakhutdinov and
+ * Mimno, "Evaluation methods for topic models" (ICML 2009), Algorithm 3, with R particles per document.
+ *   doc_off [D+1] int64, word [S] int32: TOKENS, one entry per occurrence, in the caller's order;
+ *   phi_t [V][ld_phi] doubles, word-major, REFERENCE topic order, ld_phi >= K.  Columns >= K are never read;
+ *   allowed [D][ld_allowed] uint8 or NULL: non-zero = document d may use topic k (NULL: every topic); A = how many it may use;
+ *   doc_ids [D] int64 or NULL (= doc_base + d): the document's id, whose low 32 bits key its random numbers.
+ * Every operation is one IEEE float64 operation, rounded on its own.  Topic k belongs to lane k mod 64, slot k / 64.
+ *   x(c, w)      x[k] = ((double)c[k] + alpha) * phi_t[w][k] for the allowed k, +0.0 for the others.
+ *   draw64(x, u) lane j owns x[j + 64 i]; q[j][i] = the lane's sequential inclusive prefix over i; X = the Hillis-Steele inclusive
+ *                scan of the lane totals (d = 1, 2, .., 32: X[j] = X[j-d] + X[j] for j >= d); t = u * X[63]; t_j = t - X[j-1],
+ *                X[-1] = 0; the draw is the first (j, i), lanes first, with x > 0 and q[j][i] > t_j, else the last (j, i) with x > 0,
+ *                else NONE.  The weights are not normalised (no division); a topic whose weight is 0 is never drawn.
+ *   sum64(x)     64 partials part[j] = x[j] + x[j+64] + ... in increasing k from +0.0; then part[j] = part[j] + part[j xor s] for
+ *                s = 1, 2, 4, 8, 16, 32, every j at once; the sum is part[0] (the rule of llda_heldout_loglik).
+ *   u(n, r, m)   the keyed uniform of the Philox4x32-10 counter (m >> 1, low 32 bits of the document id, stream_id + r mod 2^32, n)
+ *                under the key seed: words (0, 1) = (a, b) for an even m, words (2, 3) for an odd m,
+ *                u = ((a >> 5) * 2^26 + (b >> 6)) / 2^53.
+ *   document     particle r = 0 .. R-1 holds the counts c_r[k] = 0 and the assignments z_r[n] = NONE.  For the position
+ *                n = 0, 1, .., N-1 with the word w_n, every particle:
+ *                  resampling   for m = 0 .. n-1 in order, skipping the m with z_r[m] = NONE:  c_r[z_r[m]] -= 1;
+ *                               z = draw64(x(c_r, w_m), u(n, r, m)); z_r[m] = z (kept as it was when z is NONE); c_r[z_r[m]] += 1.
+ *                  prediction   x = x(c_r, w_n); S_r = sum64(x); pred_r = S_r / ((double)assigned_r + A_alpha), assigned_r = the
+ *                               number of m < n with z_r[m] != NONE, A_alpha = (double)A * alpha (rounded before the sum).
+ *                  extension    0 < S_r < inf: z_r[n] = draw64(x, u(n, r, n)) and, unless it is NONE, c_r[z_r[n]] += 1.
+ *                               Otherwise z_r[n] stays NONE.
+ *                A word outside [0, V) is never used as an index: the resampling runs all the same, S_r and pred_r are NaN and
+ *                z_r[n] stays NONE.
+ *                p_n = (pred_0 + pred_1 + ... + pred_{R-1}) / (double)R, added in increasing r from +0.0.  0 < p_n < inf: tok += 1
+ *                and the document's pair is multiplied by frexp(p_n) -- mul of llda_heldout_loglik, from (0.5, 1); else bad += 1.
+ *   mant [D] double, expo [D] int64, tok [D] int64, bad [D] int64: as llda_heldout_loglik's (all four required);
+ *   status [1] int32 or NULL: bit 0 is OR-ed in when a document holds more than max_doc_tokens tokens.  Such a document is not
+ *   scored: its outputs are (0.5, 1, 0, 0).  So are those of an empty document, without the bit.
+ * A document's outputs depend on its own tokens, its id, its allowed row and the scalars -- not on D, its place in the batch or the
+ * geometry -- and equal the restatement in tests/leftrightref.py bit for bit.  Cost: R * N * (N + 1) / 2 draws over K topics.
+ * One workgroup per document, one wavefront per particle (counts in registers, assignments and words in LDS sized by
+ * max_doc_tokens: pass the longest document, not the limit).  D == 0 is a no-op.
+ * LLDA_E_BAD_K: K outside 1 .. 1024 (the counts of a particle stay in registers: a narrow-layout entry point).  LLDA_E_BAD_ARG: a
+ * NULL args or a struct_bytes other than sizeof(llda_leftright_args); D < 0; V outside 1 .. 2^31 - 1; ld_phi < K, or ld_allowed < K
+ * with allowed; R outside 1 .. LLDA_LR_MAX_PARTICLES; alpha not a finite number > 0; max_doc_tokens outside 1 .. LLDA_LR_MAX_TOKENS
+ * (the estimator is quadratic in N); with D > 0 a NULL doc_off, word, phi_t, mant, expo, tok or bad, or a misaligned pointer.  All
+ * before anything touches HIP.  llda_leftright_struct_bytes (host only) lets a binding check its definition at load time. */
+#define LLDA_LR_MAX_PARTICLES 16
+#define LLDA_LR_MAX_TOKENS 4096
+typedef struct llda_leftright_args {
+    uint32_t struct_bytes;       /* sizeof(llda_leftright_args)                                  */
+    int32_t  K, R, max_doc_tokens;
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    const uint8_t *allowed;      /* [dev] [D][ld_allowed] or NULL                                */
+    const int64_t *doc_ids;      /* [dev] [D] or NULL                                            */
+    int64_t  D, V, ld_phi, ld_allowed, doc_base;
+    double   alpha;
+    uint64_t seed;
+    uint32_t stream_id, reserved;
+    double  *mant;               /* [dev] [D]                                                    */
+    int64_t *expo;               /* [dev] [D]                                                    */
+    int64_t *tok;                /* [dev] [D]                                                    */
+    int64_t *bad;                /* [dev] [D]                                                    */
+    int32_t *status;             /* [dev] [1] or NULL                                            */
+} llda_leftright_args;
+int llda_leftright_struct_bytes(void);
+int llda_left_to_right(const llda_leftright_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -13,6 +13,7 @@ What differs from the reference:
   * new, off by default: ``optimize_priors()`` and ``run_training(..., optimize_interval=n)`` fit alpha and beta to the counts while
     training (the reference fixes both); ``prior_trace`` records the fitted values;
   * new: ``heldout_perplexity()`` scores unseen documents by document completion on the device (``heldout.py``).
+  * new: ``left_to_right()`` estimates the likelihood of unseen documents with a particle sampler on the device (``leftright.py``).
   * new: ``word_credit()`` / ``explain()`` say which words are credited to which label, ``fold_in_em()`` / ``predict_em()`` fold unseen
     documents in by EM, without random numbers (``attribution.py``).
 Text preparation uses ``lda_thesis_amd.text`` instead of gensim (not installable here).
@@ -441,6 +442,37 @@ class LabeledLDA(object):
         doc_off, word, freq = csr_from_doc_tups(scored)
         r = heldout.perplexity_from(*heldout.loglik(theta, ph_dev.t().contiguous(), doc_off, word, freq, weighted=weighted))
         return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped)
+
+    # ---- left-to-right held-out likelihood (new; leftright.py) ----
+    def left_to_right(self, newdocs, particles=10, labels=None, seed=None, stream_id=None, max_tokens=None):
+        """An estimate of p(w_d | ph_hat, alpha) for every held-out token list by the left-to-right particle sampler of Wallach et al.
+        (2009): dict(perplexity, loglik, tokens, documents, skipped, bad).  The token lists keep the text's own order; tokens the
+        dictionary does not know are dropped; ``max_tokens`` scores only the first tokens of every document.  Documents with no
+        token left, or with more than 4096 after truncation, are counted in ``skipped``; the others carry the ids 0, 1, ...
+        ``labels`` (one list of label strings per document): the topics of every document are restricted to its labels and
+        'root' -- the figure is then p(w_d | labels_d).  perplexity = exp(-loglik / tokens), inf when a token had no finite positive
+        probability (``bad`` counts them).  ``ph_hat`` stays on the device (llda_left_to_right); 32 bytes per document come back.
+        Every rank scores the documents whole: no collective."""
+        import torch
+        from . import heldout, leftright
+        if labels is not None and len(labels) != len(newdocs):
+            raise ValueError("labels must hold one list per document of newdocs")
+        t2i = self.dicti.token2id
+        lists, keep = leftright.prepare_tokens([[t2i[x] for x in doc if x in t2i] for doc in newdocs], max_tokens)
+        skipped = len(newdocs) - len(keep)
+        if not keep:
+            return dict(perplexity=float("nan"), loglik=0.0, tokens=0, documents=0, skipped=skipped, bad=0)
+        allowed = None if labels is None else leftright.allowed_matrix([labels[d] for d in keep], self.labelmap, self.K)
+        ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
+        dev = self._attr_device()
+        ph_dev = ph.to(device=dev, dtype=torch.float64) if isinstance(ph, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(ph, dtype=np.float64)).to(dev)
+        doc_off, word = leftright.tokens_csr(lists)
+        r = heldout.perplexity_from(*leftright.loglik(ph_dev.t().contiguous(), doc_off, word, float(self.alpha), particles,
+                                                      self.seed if seed is None else seed,
+                                                      leftright.LR_STREAM if stream_id is None else stream_id, allowed=allowed))
+        return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped,
+                    bad=r["bad"])
 
     # ---- credit attribution and the EM fold-in (new; attribution.py, DESIGN.md 4.4e) ----
     def _attr_device(self):

@@ -90,12 +90,21 @@ class LldaAttrArgs(ctypes.Structure):
                 ("site_val", _c_p), ("tok", _c_p), ("bad", _c_p)]
 
 
+class LldaLeftrightArgs(ctypes.Structure):
+    """struct llda_leftright_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("R", _c_i32), ("max_doc_tokens", _c_i32), ("doc_off", _c_p), ("word", _c_p),
+                ("phi_t", _c_p), ("allowed", _c_p), ("doc_ids", _c_p), ("D", _c_i64), ("V", _c_i64), ("ld_phi", _c_i64),
+                ("ld_allowed", _c_i64), ("doc_base", _c_i64), ("alpha", _c_d), ("seed", _c_u64), ("stream_id", _c_u32),
+                ("reserved", _c_u32), ("mant", _c_p), ("expo", _c_p), ("tok", _c_p), ("bad", _c_p), ("status", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
            "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
-           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik", "llda_attribute")
+           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik", "llda_attribute",
+           "llda_leftright_struct_bytes", "llda_left_to_right")
 
 _LIB = None
 
@@ -177,6 +186,10 @@ def lib():
     L.llda_heldout_loglik.argtypes = [ctypes.POINTER(LldaHeldoutArgs), _c_p]
     L.llda_attribute.restype = ctypes.c_int
     L.llda_attribute.argtypes = [ctypes.POINTER(LldaAttrArgs), _c_p]
+    L.llda_leftright_struct_bytes.restype = ctypes.c_int
+    L.llda_leftright_struct_bytes.argtypes = []
+    L.llda_left_to_right.restype = ctypes.c_int
+    L.llda_left_to_right.argtypes = [ctypes.POINTER(LldaLeftrightArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -188,6 +201,9 @@ def lib():
         if L.llda_struct_size(which) != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (struct.__name__, ctypes.sizeof(struct),
                                                                            L.llda_struct_size(which)))
+    if L.llda_leftright_struct_bytes() != ctypes.sizeof(LldaLeftrightArgs):
+        raise NativeError("LldaLeftrightArgs: binding has %d bytes, the library %d" % (ctypes.sizeof(LldaLeftrightArgs),
+                                                                                       L.llda_leftright_struct_bytes()))
     _LIB = L
     return L
 
@@ -424,6 +440,24 @@ def attribute(doc_off, word, freq, theta, phi_t, D, V, K, *, iters=0, alpha=0.0,
                      int(K), int(iters), int(top_m), 0, float(alpha), _ptr(theta_out), _ptr(credit), _ptr(site_idx), _ptr(site_val),
                      _ptr(tok), _ptr(bad))
     _launch(theta, lib().llda_attribute, "llda_attribute", ctypes.byref(a))
+
+
+LR_MAX_PARTICLES = 16          # LLDA_LR_MAX_PARTICLES
+LR_MAX_TOKENS = 4096           # LLDA_LR_MAX_TOKENS
+LR_MAX_K = 1024                # llda_left_to_right keeps a particle's counts in registers
+
+
+def left_to_right(doc_off, word, phi_t, D, V, K, *, particles, alpha, seed, stream_id, max_doc_tokens, mant, expo, tok, bad,
+                  ld_phi=None, allowed=None, ld_allowed=None, doc_ids=None, doc_base=0, status=None):
+    """llda_left_to_right on the current torch stream: doc_off (int64 [D+1]) / word (int32 [S]) the TOKENS in the text's order; phi_t
+    (V, ld_phi) float64 in reference topic order; allowed (D, ld_allowed) uint8 or None; doc_ids int64 [D] or None; mant (float64
+    [D]), expo, tok, bad (int64 [D]) the outputs; status int32 [1] or None."""
+    a = LldaLeftrightArgs(ctypes.sizeof(LldaLeftrightArgs), int(K), int(particles), int(max_doc_tokens), _ptr(doc_off), _ptr(word),
+                          _ptr(phi_t), _ptr(allowed), _ptr(doc_ids), int(D), int(V), int(phi_t.stride(0) if ld_phi is None else ld_phi),
+                          int((K if allowed is None else allowed.stride(0)) if ld_allowed is None else ld_allowed), int(doc_base),
+                          float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, 0, _ptr(mant), _ptr(expo),
+                          _ptr(tok), _ptr(bad), _ptr(status))
+    _launch(phi_t, lib().llda_left_to_right, "llda_left_to_right", ctypes.byref(a))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

@@ -43,6 +43,7 @@
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
 //   kernel_heldout.hpp  llda_heldout_wave_kernel, _wide_kernel, _group_kernel   per-document likelihood of held-out sites as (mantissa, exponent)
 //   kernel_attr.hpp     llda_attr_wave_kernel, _lds_kernel, _group_kernel           per-word label shares, credit and the EM fold-in
+//   kernel_leftright.hpp llda_leftright_kernel   left-to-right estimate of a document's likelihood: one particle per wavefront
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -75,6 +76,7 @@
 #include "kernel_cooc.hpp"
 #include "kernel_heldout.hpp"
 #include "kernel_attr.hpp"
+#include "kernel_leftright.hpp"
 
 namespace {
 
@@ -972,6 +974,42 @@ int llda_attribute(const llda_attr_args *a, void *stream)
     P.top_m = sites ? a->top_m : 0; P.site_idx = sites ? a->site_idx : nullptr; P.site_val = sites ? a->site_val : nullptr;
     hipStream_t st = (hipStream_t)stream;
     return sites ? launch_attr<true>(P, st) : launch_attr<false>(P, st);
+}
+
+int llda_leftright_struct_bytes(void) { return (int)sizeof(llda_leftright_args); }
+
+int llda_left_to_right(const llda_leftright_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_leftright_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_NARROW_KP) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->ld_phi < a->K || (a->allowed && a->ld_allowed < a->K)) return LLDA_E_BAD_ARG;
+    if (a->R < 1 || a->R > LLDA_LR_MAX_PARTICLES || !(a->alpha > 0.0) || !(a->alpha < INFINITY)) return LLDA_E_BAD_ARG;
+    if (a->max_doc_tokens < 1 || a->max_doc_tokens > LLDA_LR_MAX_TOKENS) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->phi_t || !a->mant || !a->expo || !a->tok || !a->bad) return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / a->ld_phi || (a->allowed && a->D > INT64_MAX / a->ld_allowed)) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->phi_t, a->doc_ids, a->mant, a->expo, a->tok, a->bad)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->word, a->status)) return LLDA_E_BAD_ARG;
+    static_assert(LR_MAX_PARTICLES == LLDA_LR_MAX_PARTICLES && LLDA_LR_MAX_TOKENS < 0xFFFF, "kernel_leftright.hpp restates the header");
+    LrParams P;
+    P.doc_off = a->doc_off; P.word = a->word; P.phi_t = a->phi_t; P.allowed = a->allowed; P.doc_ids = a->doc_ids;
+    P.D = a->D; P.V = a->V; P.ld_phi = a->ld_phi; P.ld_allowed = a->ld_allowed; P.doc_base = a->doc_base;
+    P.K = a->K; P.R = a->R; P.cap = a->max_doc_tokens; P.alpha = a->alpha;
+    P.key0 = (uint32_t)a->seed; P.key1 = (uint32_t)(a->seed >> 32); P.stream_id = a->stream_id;
+    P.mant = a->mant; P.expo = a->expo; P.tok = a->tok; P.bad = a->bad; P.status = a->status;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = lr_lds_bytes(P.R, P.cap);                            // at most 147 712 bytes
+    const dim3 grid((unsigned)(P.D < (1 << 20) ? P.D : (1 << 20))), block(64 * P.R);
+    const int NI = P.K <= 64 ? 1 : P.K <= 128 ? 2 : P.K <= 256 ? 4 : P.K <= 512 ? 8 : 16;
+    return visit_int<1, 2, 4, 8, 16>(NI, [&](auto ni) {
+        return visit_int<8, 16>(P.R <= 8 ? 8 : 16, [&](auto waves) {
+            const auto kern = llda_leftright_kernel<ni.value, waves.value>;
+            const int rl = allow_lds(kern, lds);
+            if (rl) return rl;
+            hipLaunchKernelGGL(kern, grid, block, lds, st, P);
+            return launched();
+        });
+    });
 }
 
 int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab_mask, const int32_t *n_dk,

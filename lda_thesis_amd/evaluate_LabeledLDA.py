@@ -31,6 +31,9 @@ def build_parser():
     p.add_option("--heldout-perplexity", action="store_true", dest="heldout_perplexity", default=False,
                  help="after the report: perplexity of the held-out documents by document completion (every second word of a "
                       "document folded in, the others scored on the GPU: llda_heldout_loglik)")
+    p.add_option("--left-to-right", dest="left_to_right", type="int", default=0, metavar="R",
+                 help="after the report: perplexity of the held-out documents from the left-to-right estimate of their likelihood "
+                      "with R particles (Wallach et al. 2009; llda_left_to_right)")
     p.add_option("--em-foldin", dest="em_foldin", type="int", default=0, metavar="ITERS",
                  help="after the report: the same four metrics for the loads of the deterministic EM fold-in with ITERS steps "
                       "(llda_attribute), ranked and scored on the GPU")
@@ -71,6 +74,16 @@ def report_explain(model, test, n_docs, iters):
                         got[token] = got.get(token, 0.0) + f * share
             best = sorted(got, key=lambda t: (-got[t], t))[:5]
             print("  %-24s %8.2f  %s" % (label, credit[label], " ".join(best)))
+
+
+def report_left_to_right(model, test, particles):
+    """held-out perplexity of the test documents from the left-to-right estimate of p(w_d | phi, alpha)"""
+    r = model.left_to_right(test[0], particles=particles)
+    print("-----------------------------------")
+    print("Held-out perplexity (left-to-right, %d particles): " % particles, r["perplexity"])
+    print("  scored tokens %d in %d documents (%d skipped, %d bad tokens), log-likelihood %s"
+          % (r["tokens"], r["documents"], r["skipped"], r["bad"], r["loglik"]))
+    return r
 
 
 def report_heldout(model, test, it, thinning):
@@ -148,6 +161,8 @@ def main(argv=None):
         report_coherence(model, opt.coherence)
     if opt.heldout_perplexity:
         report_heldout(model, test, opt.it, opt.thinning)
+    if opt.left_to_right:
+        report_left_to_right(model, test, opt.left_to_right)
     if opt.em_foldin:
         report_em_foldin(model, test, opt.em_foldin)
     if opt.explain:
