@@ -724,6 +724,47 @@ typedef struct llda_leftright_args {
 int llda_leftright_struct_bytes(void);
 int llda_left_to_right(const llda_leftright_args *args, void *stream);
 
+/* The n best rows of a matrix b for every row of a matrix a under a bilinear score (additive to ABI 22): similar
+ * documents (rows = sqrt(theta): the score is the Bhattacharyya coefficient, Hellinger distance = sqrt(1 - score)), similar labels
+ * (rows = sqrt(phi), L = V), nearest-neighbour prediction.
+ *   a [Q][lda], b [D][ldb] doubles, row-major; lda, ldb >= L; columns >= L are never read.  L in 1 .. 2^31 - 1 (not bound by
+ *   LLDA_MAX_K); n in 1 .. LLDA_NEAREST_MAX_N; row_base >= 0 = the global id of row 0 of b (row_base + D must fit an int64);
+ *   exclude [Q] int64 or NULL: a global row id that query q must not return (-1, or any id outside the range: none).
+ * Score of the pair (q, j): s = +0.0, then for k = 0, 1, .., L-1 in this order s = fma(a[q][k], b[j][k], s) -- one fused multiply-add,
+ * one rounding per element.  It depends on the two rows only: not on Q, D, the tiles, `chunks` or which call holds the row.
+ * Order per query: score descending, compared as IEEE values (-0 == +0, +-inf ordinary), then global row id ascending.  A NaN score is
+ * not a candidate (it is counted), and neither is the exclude row.
+ *   top_idx [Q][n] int64 global row ids, top_val [Q][n] double, n_nan [Q] int64 = the NaN scores left out; each may be NULL.
+ *   Entries beyond the number of candidates are -1 / 0.0.
+ *   chunks: 0 = the library chooses; > 0 = b is walked as exactly min(chunks, D) row ranges.  A geometry knob: no output depends on it.
+ *   scratch: at least llda_nearest_scratch_bytes(Q, D, n, chunks) bytes, contents irrelevant before and after.  One partial list per
+ *   (query, range) is left there and a second small launch merges them; no score is written to memory.
+ * Alignment: every pointer 8-byte aligned, and that is all the kernel needs (odd lda / ldb included).  When a and b are both 16-byte
+ * aligned and lda and ldb are both even, the rows are fetched with 16-byte loads (the fast path); the results are the same bits.
+ * Q == 0 is a no-op; D == 0 launches only the padding.  LLDA_E_BAD_ARG, before anything touches HIP: a NULL args, a struct_bytes
+ * other than sizeof(llda_nearest_args), a NULL a, b or scratch; n outside 1 .. 16; L < 1; lda or ldb < L; negative Q, D, chunks or
+ * row_base; sizes whose products leave an int64 or a grid of 2^31 - 1 workgroups; a misaligned pointer; scratch_bytes too small.
+ * llda_nearest_scratch_bytes and llda_nearest_struct_bytes are host only; the former returns LLDA_E_BAD_ARG for the same bad sizes. */
+#define LLDA_NEAREST_MAX_N 16
+#define LLDA_NEAREST_TILE 128    /* queries and rows of a tile */
+#define LLDA_NEAREST_KSTEP 16    /* columns per step of the k-loop */
+typedef struct llda_nearest_args {
+    uint32_t struct_bytes;       /* sizeof(llda_nearest_args)                                    */
+    int32_t  L, n, chunks;
+    const double  *a;            /* [dev] [Q][lda]                                               */
+    const double  *b;            /* [dev] [D][ldb]                                               */
+    const int64_t *exclude;      /* [dev] [Q] or NULL                                            */
+    int64_t  Q, D, lda, ldb, row_base;
+    int64_t *top_idx;            /* [dev] [Q][n] or NULL                                         */
+    double  *top_val;            /* [dev] [Q][n] or NULL                                         */
+    int64_t *n_nan;              /* [dev] [Q] or NULL                                            */
+    void    *scratch;            /* [dev]                                                        */
+    int64_t  scratch_bytes;
+} llda_nearest_args;
+int llda_nearest_struct_bytes(void);
+int64_t llda_nearest_scratch_bytes(int64_t Q, int64_t D, int32_t n, int32_t chunks);
+int llda_nearest_rows(const llda_nearest_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -16,6 +16,8 @@ What differs from the reference:
   * new: ``left_to_right()`` estimates the likelihood of unseen documents with a particle sampler on the device (``leftright.py``).
   * new: ``word_credit()`` / ``explain()`` say which words are credited to which label, ``fold_in_em()`` / ``predict_em()`` fold unseen
     documents in by EM, without random numbers (``attribution.py``).
+  * new: ``similar_documents()``, ``similar_labels()``, ``predict_knn()`` / ``score_test_knn()`` find the nearest training documents
+    (or labels) of a text under the Hellinger affinity on the device (``similar.py``).
 Text preparation uses ``lda_thesis_amd.text`` instead of gensim (not installable here).
 """
 import csv
@@ -587,6 +589,108 @@ class LabeledLDA(object):
                                     phi_t=phi_t)
         return attribution.explanations(tups, r["site_idx"].cpu().numpy(), r["site_val"].cpu().numpy(), r["credit"].cpu().numpy(),
                                         list(self.labelmap.keys()), self.v_to_w)
+
+    # ---- nearest rows on the device (new; similar.py) ----
+    def _similar_corpus(self, measure):
+        """the affinity rows of this rank's training documents: ``th_hat`` while it is on the device, else the current theta"""
+        from . import similar
+        th = self._th_hat.dev if self._th_hat.dev is not None else self._sampler.theta()
+        return similar.affinity_rows(th, measure)
+
+    def _neighbours(self, queries, corpus, n, exclude=None):
+        """(ids (Q, n) int64, affinity (Q, n) float64) of the affinity rows ``queries`` (the same on every rank) against this rank's
+        ``corpus`` rows; with several ranks the per-rank lists are gathered and merged: 16 * Q * n bytes per rank travel."""
+        from . import similar
+        idx, val, _ = similar.nearest_rows(queries, corpus, n, exclude=exclude, row_base=int(self._bounds[_rank()]))
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        if _world_size() > 1:
+            import torch.distributed as dist
+            parts = [None] * _world_size()
+            dist.all_gather_object(parts, (idx, val))
+            idx, val = similar.merge_lists([p[0] for p in parts], [p[1] for p in parts], n)
+        return idx, val
+
+    def similar_documents(self, newdocs=None, doc_ids=None, n=10, it=500, thinning=25, measure="hellinger", seed=None, stream_id=None):
+        """The n <= 16 training documents most like each query: (ids (Q, n) int64, affinity (Q, n) float64), best first, equal
+        affinities by document id ascending, padded with -1 / 0.0 when the corpus is smaller.  Exactly one of ``newdocs`` (held-out
+        token lists, folded in as ``predict`` folds them in) and ``doc_ids`` (training documents, which never return themselves).
+        measure = "hellinger": the Bhattacharyya coefficient sum_k sqrt(theta_q[k] theta_d[k]) in [0, 1], Hellinger distance =
+        sqrt(1 - affinity); "cosine"; "dot".  The corpus is ``th_hat`` while the thinning read-outs hold it on the device, else the
+        current ``theta``; neither it nor the Q x D affinities leave the device (llda_nearest_rows).  COLLECTIVE with several ranks."""
+        import torch
+        from . import similar
+        if (newdocs is None) == (doc_ids is None):
+            raise ValueError("give exactly one of newdocs and doc_ids")
+        similar._check_n(n)
+        if measure not in similar.MEASURES:
+            raise ValueError("measure must be one of %s" % (similar.MEASURES,))
+        self._sampler.check_status()
+        corpus = self._similar_corpus(measure)
+        if doc_ids is not None:
+            ids = np.asarray(doc_ids, dtype=np.int64).reshape(-1)
+            if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.D):
+                raise ValueError("doc_ids must be in 0 .. %d" % (self.D - 1))
+            lo, hi = int(self._bounds[_rank()]), int(self._bounds[_rank() + 1])
+            mine = (ids >= lo) & (ids < hi)
+            queries = torch.zeros((ids.shape[0], self.K), dtype=torch.float64, device=corpus.device)
+            if mine.any():
+                queries[torch.from_numpy(np.flatnonzero(mine)).to(corpus.device)] = corpus[torch.from_numpy(ids[mine] - lo).to(corpus.device)]
+            if _world_size() > 1:
+                import torch.distributed as dist
+                dist.all_reduce(queries)                  # (every rank but the owner adds zeros: exact)
+            return self._neighbours(queries, corpus, n, exclude=ids)
+        if len(newdocs) == 0:
+            return np.zeros((0, n), dtype=np.int64), np.zeros((0, n), dtype=np.float64)
+        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        return self._neighbours(similar.affinity_rows(th.to(corpus.device), measure), corpus, n)
+
+    def similar_labels(self, n=5, measure="hellinger"):
+        """For every label its n <= 16 nearest other labels by word distribution: [(label, [(other label, affinity), ...]), ...] in
+        label order, best first.  The rows are ``ph_hat`` (``get_phi()`` before any thinning read-out), the inner length is V, every
+        label leaves itself out.  n_k_v is replicated: no collective."""
+        import torch
+        from . import similar
+        similar._check_n(n)
+        self._sampler.check_status()
+        dev = self._attr_device()
+        if not self.cur_perplx:
+            ph = self._sampler.phi()
+        else:
+            ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
+        if not isinstance(ph, torch.Tensor):
+            ph = torch.from_numpy(np.ascontiguousarray(ph, dtype=np.float64))
+        rows = similar.affinity_rows(ph.to(device=dev, dtype=torch.float64), measure)
+        idx, val, _ = similar.nearest_rows(rows, rows, n, exclude=np.arange(self.K, dtype=np.int64))
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        names = list(self.labelmap.keys())
+        return [(names[k], [(names[int(j)], float(v)) for j, v in zip(idx[k], val[k]) if j >= 0]) for k in range(self.K)]
+
+    def _knn_votes(self, newdocs, it, thinning, k, measure, seed, stream_id):
+        from . import similar
+        similar._check_n(k)
+        idx, val = self.similar_documents(newdocs=newdocs, n=k, it=it, thinning=thinning, measure=measure, seed=seed, stream_id=stream_id)
+        return similar.knn_votes(idx, val, self.labs, k)
+
+    def predict_knn(self, newdocs, it, thinning, k=10, n=5, measure="hellinger", seed=None, stream_id=None):
+        """``predict`` by the k <= 16 nearest training documents instead of the document's own loads: every label's score is the sum
+        of the affinities of the neighbours that carry it (``similar.knn_votes`` against ``labs``), ranked on the device; what
+        ``predict`` returns.  COLLECTIVE with several ranks."""
+        from . import ranking
+        if len(newdocs) == 0:
+            return []
+        votes = self._knn_votes(newdocs, it, thinning, k, measure, seed, stream_id)
+        r = ranking.rank_labels(votes, None, first=0, top_n=n).host()
+        names = np.array(list(self.labelmap.keys()))
+        m = min(n, self.K)
+        return [list(zip(names[idx[:m]], val[:m])) for idx, val in zip(r["top_idx"], r["top_val"])]
+
+    def score_test_knn(self, newdocs, labels, it, thinning, k=10, measure="hellinger", seed=None, stream_id=None):
+        """``score_test`` for the votes of the k <= 16 nearest training documents: the baseline beside the model's own figures, the
+        same dict through ``ranking.metrics``.  COLLECTIVE with several ranks."""
+        from . import ranking
+        from .evaluate import binary_yreal
+        votes = self._knn_votes(newdocs, it, thinning, k, measure, seed, stream_id)
+        return ranking.metrics(ranking.rank_labels(votes, binary_yreal(labels, self.labelmap), first=1, top_n=0))
 
     # ---- pickling: pull the device state to the host (evaluate_LabeledLDA.py:142-145 pickles the model)
     def __getstate__(self):

@@ -98,13 +98,21 @@ class LldaLeftrightArgs(ctypes.Structure):
                 ("reserved", _c_u32), ("mant", _c_p), ("expo", _c_p), ("tok", _c_p), ("bad", _c_p), ("status", _c_p)]
 
 
+class LldaNearestArgs(ctypes.Structure):
+    """struct llda_nearest_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("L", _c_i32), ("n", _c_i32), ("chunks", _c_i32), ("a", _c_p), ("b", _c_p), ("exclude", _c_p),
+                ("Q", _c_i64), ("D", _c_i64), ("lda", _c_i64), ("ldb", _c_i64), ("row_base", _c_i64), ("top_idx", _c_p),
+                ("top_val", _c_p), ("n_nan", _c_p), ("scratch", _c_p), ("scratch_bytes", _c_i64)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
            "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
            "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik", "llda_attribute",
-           "llda_leftright_struct_bytes", "llda_left_to_right")
+           "llda_leftright_struct_bytes", "llda_left_to_right",
+           "llda_nearest_struct_bytes", "llda_nearest_scratch_bytes", "llda_nearest_rows")
 
 _LIB = None
 
@@ -190,6 +198,12 @@ def lib():
     L.llda_leftright_struct_bytes.argtypes = []
     L.llda_left_to_right.restype = ctypes.c_int
     L.llda_left_to_right.argtypes = [ctypes.POINTER(LldaLeftrightArgs), _c_p]
+    L.llda_nearest_struct_bytes.restype = ctypes.c_int
+    L.llda_nearest_struct_bytes.argtypes = []
+    L.llda_nearest_scratch_bytes.restype = _c_i64
+    L.llda_nearest_scratch_bytes.argtypes = [_c_i64, _c_i64, _c_i32, _c_i32]
+    L.llda_nearest_rows.restype = ctypes.c_int
+    L.llda_nearest_rows.argtypes = [ctypes.POINTER(LldaNearestArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -204,6 +218,9 @@ def lib():
     if L.llda_leftright_struct_bytes() != ctypes.sizeof(LldaLeftrightArgs):
         raise NativeError("LldaLeftrightArgs: binding has %d bytes, the library %d" % (ctypes.sizeof(LldaLeftrightArgs),
                                                                                        L.llda_leftright_struct_bytes()))
+    if L.llda_nearest_struct_bytes() != ctypes.sizeof(LldaNearestArgs):
+        raise NativeError("LldaNearestArgs: binding has %d bytes, the library %d" % (ctypes.sizeof(LldaNearestArgs),
+                                                                                     L.llda_nearest_struct_bytes()))
     _LIB = L
     return L
 
@@ -458,6 +475,30 @@ def left_to_right(doc_off, word, phi_t, D, V, K, *, particles, alpha, seed, stre
                           float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, 0, _ptr(mant), _ptr(expo),
                           _ptr(tok), _ptr(bad), _ptr(status))
     _launch(phi_t, lib().llda_left_to_right, "llda_left_to_right", ctypes.byref(a))
+
+
+NEAREST_MAX_N = 16            # LLDA_NEAREST_MAX_N
+NEAREST_TILE = 128            # LLDA_NEAREST_TILE: queries and rows of a tile of llda_nearest_rows
+NEAREST_KSTEP = 16            # LLDA_NEAREST_KSTEP: columns per step of its k-loop
+
+
+def nearest_scratch_bytes(Q, D, n, chunks=0):
+    """llda_nearest_scratch_bytes: bytes of work space llda_nearest_rows needs (host only)."""
+    r = int(lib().llda_nearest_scratch_bytes(int(Q), int(D), int(n), int(chunks)))
+    if r < 0:
+        check(r, "llda_nearest_scratch_bytes(Q=%d, D=%d, n=%d, chunks=%d)" % (Q, D, n, chunks))
+    return r
+
+
+def nearest_rows(a, b, Q, D, L, n, scratch, *, lda=None, ldb=None, row_base=0, exclude=None, chunks=0, top_idx=None, top_val=None,
+                 n_nan=None):
+    """llda_nearest_rows on the current torch stream: a (Q, lda) and b (D, ldb) float64 on the device, exclude int64 [Q] or None;
+    top_idx (Q, n) int64, top_val (Q, n) float64, n_nan (Q,) int64 the outputs, each may be None; scratch = a uint8 tensor of
+    nearest_scratch_bytes(Q, D, n, chunks) bytes."""
+    args = LldaNearestArgs(ctypes.sizeof(LldaNearestArgs), int(L), int(n), int(chunks), _ptr(a), _ptr(b), _ptr(exclude), int(Q), int(D),
+                           int(a.stride(0) if lda is None else lda), int(b.stride(0) if ldb is None else ldb), int(row_base),
+                           _ptr(top_idx), _ptr(top_val), _ptr(n_nan), _ptr(scratch), int(scratch.numel() * scratch.element_size()))
+    _launch(scratch, lib().llda_nearest_rows, "llda_nearest_rows", ctypes.byref(args))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

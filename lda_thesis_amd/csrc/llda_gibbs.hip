@@ -44,6 +44,7 @@
 //   kernel_heldout.hpp  llda_heldout_wave_kernel, _wide_kernel, _group_kernel   per-document likelihood of held-out sites as (mantissa, exponent)
 //   kernel_attr.hpp     llda_attr_wave_kernel, _lds_kernel, _group_kernel           per-word label shares, credit and the EM fold-in
 //   kernel_leftright.hpp llda_leftright_kernel   left-to-right estimate of a document's likelihood: one particle per wavefront
+//   kernel_nearest.hpp  llda_nearest_kernel, llda_nearest_merge_kernel   the n best rows of b per row of a: tiled fp64 product, selection in its epilogue
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -77,6 +78,7 @@
 #include "kernel_heldout.hpp"
 #include "kernel_attr.hpp"
 #include "kernel_leftright.hpp"
+#include "kernel_nearest.hpp"
 
 namespace {
 
@@ -1010,6 +1012,61 @@ int llda_left_to_right(const llda_leftright_args *a, void *stream)
             return launched();
         });
     });
+}
+
+int llda_nearest_struct_bytes(void) { return (int)sizeof(llda_nearest_args); }
+
+// the row ranges llda_nearest_rows walks b in: the caller's count capped at D, or enough workgroups to fill the chip a few times
+// while a range keeps eight tiles or more (every range fills its lists anew, and that costs about a tile's product)
+static int64_t near_chunks(int64_t Q, int64_t D, int32_t chunks)
+{
+    if (D == 0) return 0;
+    if (chunks > 0) return chunks < D ? chunks : D;
+    const int64_t q_tiles = (Q + NEAR_T - 1) / NEAR_T, tiles = (D + NEAR_T - 1) / NEAR_T;
+    int64_t want = q_tiles > 0 ? 2048 / q_tiles : 1;
+    if (want > tiles / 8) want = tiles / 8;
+    return want < 1 ? 1 : want;
+}
+
+int64_t llda_nearest_scratch_bytes(int64_t Q, int64_t D, int32_t n, int32_t chunks)
+{
+    if (Q < 0 || D < 0 || chunks < 0 || n < 1 || n > LLDA_NEAREST_MAX_N) return LLDA_E_BAD_ARG;
+    const int64_t C = near_chunks(Q, D, chunks), per = 16 * (int64_t)n + 8;
+    if (C > 0 && Q > (INT64_MAX - 16) / per / C) return LLDA_E_BAD_ARG;
+    return Q * C * per + 16;                              // (never 0: a caller's allocation always has an address)
+}
+
+int llda_nearest_rows(const llda_nearest_args *a, void *stream)
+{
+    static_assert(NEAR_T == LLDA_NEAREST_TILE && NEAR_KS == LLDA_NEAREST_KSTEP && NEAR_MAX_N == LLDA_NEAREST_MAX_N,
+                  "kernel_nearest.hpp restates the header");
+    if (!a || a->struct_bytes != sizeof(llda_nearest_args)) return LLDA_E_BAD_ARG;
+    if (!a->a || !a->b || !a->scratch || a->n < 1 || a->n > LLDA_NEAREST_MAX_N || a->L < 1) return LLDA_E_BAD_ARG;
+    if (a->lda < a->L || a->ldb < a->L || a->Q < 0 || a->D < 0 || a->chunks < 0 || a->row_base < 0) return LLDA_E_BAD_ARG;
+    if (a->row_base > INT64_MAX - a->D || a->Q > INT64_MAX / a->lda || a->D > INT64_MAX / a->ldb) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->a, a->b, a->exclude, a->top_idx, a->top_val, a->n_nan) || misaligned(7, a->scratch)) return LLDA_E_BAD_ARG;
+    const int64_t need = llda_nearest_scratch_bytes(a->Q, a->D, a->n, a->chunks);
+    if (need < 0 || a->scratch_bytes < need) return LLDA_E_BAD_ARG;
+    const int64_t C = near_chunks(a->Q, a->D, a->chunks), q_tiles = (a->Q + NEAR_T - 1) / NEAR_T;
+    if (C > 0 && q_tiles > INT32_MAX / C) return LLDA_E_BAD_ARG;
+    if (a->Q == 0) return LLDA_OK;
+    NearParams P;
+    memset(&P, 0, sizeof P);
+    P.a = a->a; P.b = a->b; P.Q = a->Q; P.D = a->D; P.lda = a->lda; P.ldb = a->ldb; P.row_base = a->row_base;
+    P.exclude = a->exclude; P.L = a->L; P.n = a->n; P.chunks = (int32_t)C;
+    P.part_val = static_cast<double *>(a->scratch);
+    P.part_idx = reinterpret_cast<int64_t *>(P.part_val + a->Q * C * a->n);
+    P.part_nan = P.part_idx + a->Q * C * a->n;
+    P.top_idx = a->top_idx; P.top_val = a->top_val; P.n_nan = a->n_nan;
+    hipStream_t st = (hipStream_t)stream;
+    if (C > 0) {
+        const dim3 grid((unsigned)(q_tiles * C));
+        const bool vec = !misaligned(15, a->a, a->b) && !(a->lda & 1) && !(a->ldb & 1);
+        if (vec) hipLaunchKernelGGL(llda_nearest_kernel<true>, grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL(llda_nearest_kernel<false>, grid, dim3(256), 0, st, P);
+    }
+    hipLaunchKernelGGL(llda_nearest_merge_kernel, dim3((unsigned)((a->Q + 63) / 64)), dim3(64), 0, st, P);
+    return launched();
 }
 
 int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab_mask, const int32_t *n_dk,

@@ -40,7 +40,33 @@ def build_parser():
     p.add_option("--explain", dest="explain", type="int", default=0, metavar="N",
                  help="after the report: for the first N test documents the suggested labels with the five most-credited words "
                       "of each (llda_attribute)")
+    p.add_option("--knn", dest="knn", type="int", default=0, metavar="K",
+                 help="after the report: the same four metrics for the votes of the K nearest training documents of every test "
+                      "document (Hellinger affinity of the loads; llda_nearest_rows)")
+    p.add_option("--similar-labels", dest="similar_labels", type="int", default=0, metavar="N",
+                 help="after the report: every label with its N nearest labels by word distribution (llda_nearest_rows)")
     return p
+
+
+def report_knn(model, test, it, thinning, k):
+    """the four metrics of the report for the votes of the k nearest training documents (LabeledLDA.score_test_knn)"""
+    known = set(model.vocab)
+    m = model.score_test_knn([[x for x in doc if x in known] for doc in test[0]], test[1], it, thinning, k=k)
+    print("-----------------------------------")
+    print("k nearest training documents (k = %d, Hellinger affinity):" % k)
+    print("AUC ROC:                 ", m["auc"])
+    print("one error:               ", m["one_error"])
+    print("two error:               ", m["two_error"])
+    print("F1 score (macro average) ", m["f1"])
+    return m
+
+
+def report_similar_labels(model, n):
+    """every label with its n nearest labels by word distribution (LabeledLDA.similar_labels)"""
+    print("-----------------------------------")
+    print("Nearest labels by word distribution (Hellinger affinity, top %d):" % n)
+    for name, near in model.similar_labels(n):
+        print("  %-24s %s" % (name, "  ".join("%s %.4f" % (other, aff) for other, aff in near)))
 
 
 def report_em_foldin(model, test, iters):
@@ -167,6 +193,10 @@ def main(argv=None):
         report_em_foldin(model, test, opt.em_foldin)
     if opt.explain:
         report_explain(model, test, opt.explain, opt.em_foldin or 50)
+    if opt.knn:
+        report_knn(model, test, opt.it, opt.thinning, opt.knn)
+    if opt.similar_labels:
+        report_similar_labels(model, opt.similar_labels)
 
 
 if __name__ == "__main__":
