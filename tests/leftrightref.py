@@ -34,8 +34,14 @@ def _grid(x, NI):
     return out.reshape(P, NI, LANES)
 
 
-def draw64(x, u):
-    """x (P, K) weights, u (P,) uniforms -> int64 (P,) topics, -1 where no weight is > 0"""
+def masked(x, m):
+    """the weights of the topics that are not allowed are +0.0 (on its own so that a test can take the mask away)"""
+    return np.where(m, x, 0.0)
+
+
+def draw64(x, u, stats=None):
+    """x (P, K) weights, u (P,) uniforms -> int64 (P,) topics, -1 where no weight is > 0.  stats: a dict whose 'draws' and 'no_hit'
+    are raised by the draws that had a weight > 0 and by those of them that no q > t_j decided (the "last with x > 0" rule)"""
     x = np.asarray(x, dtype=np.float64)
     P, K = x.shape
     NI = slots(K)
@@ -61,6 +67,9 @@ def draw64(x, u):
     first = np.argmax(flag, axis=1)
     last = pos.shape[1] - 1 - np.argmax(pos[:, ::-1], axis=1)
     at = np.where(flag.any(axis=1), first, last)
+    if stats is not None:
+        stats["draws"] = stats.get("draws", 0) + int(pos.any(axis=1).sum())
+        stats["no_hit"] = stats.get("no_hit", 0) + int((pos.any(axis=1) & ~flag.any(axis=1)).sum())
     topic = at // NI + LANES * (at % NI)
     return np.where(pos.any(axis=1), topic, NONE).astype(np.int64)
 
@@ -80,9 +89,11 @@ def sum64(x):
 
 
 def left_to_right_ref(phi_t, doc_off, word, alpha, R, seed, stream_id, K=None, V=None, allowed=None, doc_ids=None, max_doc_tokens=None,
-                      trace=None):
+                      trace=None, stats=None):
     """phi_t (V, >= K) float64; token CSR; allowed (D, >= K) or None; doc_ids [D] or None (= 0, 1, ...) -> (mant float64 [D], expo, tok,
-    bad int64 [D], status).  trace: a dict that receives 'z' (D, R, Nmax) and 'p' (D, Nmax), the final assignments and the p_n."""
+    bad int64 [D], status).  trace: a dict that receives 'z' (D, R, Nmax) and 'p' (D, Nmax), the final assignments and the p_n;
+    stats: a dict for draw64's counts (the resampling draws and the extensions together)."""
+    draw = draw64 if stats is None else (lambda x, u: draw64(x, u, stats))
     phi_t = np.asarray(phi_t, dtype=np.float64)
     D = len(doc_off) - 1
     K = phi_t.shape[1] if K is None else int(K)
@@ -116,7 +127,7 @@ def left_to_right_ref(phi_t, doc_off, word, alpha, R, seed, stream_id, K=None, V
     def weights(p, w):
         with np.errstate(all="ignore"):
             x = (c[p] + alpha) * phi_t[w, :K]
-        return np.where(mask[pd[p]], x, 0.0)
+        return masked(x, mask[pd[p]])
 
     for n in range(Nmax):
         live = np.nonzero(lens[pd] > n)[0]                              # the particles of the documents that have a position n
@@ -128,7 +139,7 @@ def left_to_right_ref(phi_t, doc_off, word, alpha, R, seed, stream_id, K=None, V
             p = live[sel]
             zo = z[p, m]
             c[p, zo] -= 1.0
-            zn = draw64(weights(p, words[pd[p], m]), u[sel, m])
+            zn = draw(weights(p, words[pd[p], m]), u[sel, m])
             zn = np.where(zn < 0, zo, zn)
             c[p, zn] += 1.0
             z[p, m] = zn
@@ -141,7 +152,7 @@ def left_to_right_ref(phi_t, doc_off, word, alpha, R, seed, stream_id, K=None, V
             go = (S > 0.0) & (S < np.inf)
         if go.any():
             p = live[go]
-            zn = draw64(x[go], u[go, n])
+            zn = draw(x[go], u[go, n])
             hit = zn >= 0
             c[p[hit], zn[hit]] += 1.0
             z[p[hit], n] = zn[hit]
