@@ -765,6 +765,102 @@ int llda_nearest_struct_bytes(void);
 int64_t llda_nearest_scratch_bytes(int64_t Q, int64_t D, int32_t n, int32_t chunks);
 int llda_nearest_rows(const llda_nearest_args *args, void *stream);
 
+/* Label-wise evaluation (additive to ABI 22): for every ranked label the D documents ordered by that label's score,
+ * and from the ordered row the label's AUC, its best F1 and the threshold that reaches it (SCut).  llda_rank_labels ranks the K labels
+ * of a document; this is the other sort: D keys for each of n_labels segments, 64-bit keys, the document id as payload.
+ *   score [D][ld] doubles in REFERENCE topic order, ld >= K; truth [D][K] uint8, REQUIRED here, non-zero = the document carries the label.
+ * The ranked columns are first .. first + n_labels - 1 <= K - 1; output row l belongs to column first + l, and no other column is read:
+ * a caller short of scratch walks the labels in batches and gets the same bits.  1 <= D <= 2^30 (the payload doc << 1 | truth keeps
+ * 32 bits and every product below 64); D == 0 or n_labels == 0 is a no-op.  Scores compare as IEEE values (-0 == +0, +-inf ordinary).
+ * Per ranked label:
+ *   order    [n_labels][D] int32: the document ids by score descending, then document id ascending: np.argsort(-col, kind="stable")
+ *   A tie group is a maximal run of equal scores in the order; its end is a threshold: a document is predicted when its score is >=
+ *   the group's.  tp_g / fp_g = predicted documents with / without the label, cumulative; tp_0 = fp_0 = 0.
+ *   n_pos    P, documents with the label (N = D - P);  n_thr  T, the number of distinct scores; both int64
+ *   auc_num  uint64 A = sum_{g=1..T} (fp_g - fp_{g-1}) (tp_g + tp_{g-1}) = 2 #(positive above negative) + #(positive tied with negative),
+ *            the Mann-Whitney count; A <= 2 P N < 2^61
+ *   auc      (double)A / (double)(2 P N), one IEEE division; NaN when P = 0 or N = 0.  The curve starts at (0, 0): the standard
+ *            label-wise AUC.  This is deliberately NOT llda_rank_labels's per-document auc, which starts at the first threshold as the
+ *            reference's macro_auc_roc does; that quirk stays where the reference has it.  (T = 1 with P, N > 0 gives 0.5 here.)
+ *   f1       the largest 2 tp_g / (tp_g + fp_g + P) over the groups with tp_g > 0, chosen by integer cross-multiplication; equal
+ *            rationals go to the highest threshold (the earliest group); then one IEEE division.  thr_tp, thr_fp (int64) are that
+ *            group's tp_g and fp_g, thr (double) the score BITS of the group's first document in the order (its lowest document id:
+ *            a -0.0 stays one).  No group with tp > 0 (P = 0): f1 = thr = NaN, thr_tp = thr_fp = 0.
+ *   flags    int32, the bits of llda_rank_labels: 1: P = 0, 2: N = 0, 4: T < 2, 8: every score of the column equals 0,
+ *            16: a NaN in the column -- then flags = 16, the five integers are 0, auc = f1 = thr = NaN and the order row is -1.
+ * Every output pointer may be NULL on its own.  Every output is an integer, a copy of an input or one correctly rounded division of
+ * two exact integers: bit-identical whatever the chunk, the batches or the geometry.
+ *   chunk    0 = LLDA_LABEL_CHUNK pairs are sorted by one workgroup in LDS before the merge levels; 256 = the one other value, for tests
+ *            (a deep merge tree at a few thousand documents).  Anything else: LLDA_E_BAD_ARG.
+ *   scratch  at least llda_label_scratch_bytes(D, n_labels, chunk) bytes = 2 x 12 x Dp x n_labels + 16, Dp = D rounded up to the chunk;
+ *            contents irrelevant before and after.  (D = 100 000, 511 labels: 1.26 GB.)
+ * Alignment: score, scratch and the 8-byte outputs 8-byte aligned, flags and order 4-byte aligned.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG, before anything touches HIP: a NULL args; a struct_bytes other than
+ * sizeof(llda_label_args); first < 0, n_labels < 0 or first + n_labels > K; ld < K; D < 0 or D > 2^30; a chunk other than 0 and 256;
+ * and with D > 0 and n_labels > 0: a NULL score, truth or scratch, a misaligned pointer, scratch_bytes too small.
+ * llda_label_scratch_bytes and llda_label_struct_bytes are host only; the former returns LLDA_E_BAD_ARG for the same bad sizes. */
+#define LLDA_LABEL_CHUNK 4096        /* pairs one workgroup sorts in LDS: 48 KB, three workgroups per compute unit */
+#define LLDA_LABEL_TEST_CHUNK 256
+#define LLDA_LABEL_MAX_D (1 << 30)
+typedef struct llda_label_args {
+    uint32_t struct_bytes;       /* sizeof(llda_label_args)                                      */
+    int32_t  K, first, n_labels;
+    int32_t  chunk, reserved;
+    const double  *score;        /* [dev] [D][ld]                                                */
+    const uint8_t *truth;        /* [dev] [D][K]                                                 */
+    int64_t  D, ld;
+    int64_t  *n_pos;             /* [dev] [n_labels] or NULL                                     */
+    int64_t  *n_thr;             /* [dev] [n_labels] or NULL                                     */
+    uint64_t *auc_num;           /* [dev] [n_labels] or NULL                                     */
+    double   *auc;               /* [dev] [n_labels] or NULL                                     */
+    int64_t  *thr_tp;            /* [dev] [n_labels] or NULL                                     */
+    int64_t  *thr_fp;            /* [dev] [n_labels] or NULL                                     */
+    double   *f1;                /* [dev] [n_labels] or NULL                                     */
+    double   *thr;               /* [dev] [n_labels] or NULL                                     */
+    int32_t  *flags;             /* [dev] [n_labels] or NULL                                     */
+    int32_t  *order;             /* [dev] [n_labels][D] or NULL                                  */
+    void     *scratch;           /* [dev]                                                        */
+    int64_t  scratch_bytes;
+} llda_label_args;
+int llda_label_struct_bytes(void);
+int64_t llda_label_scratch_bytes(int64_t D, int32_t n_labels, int32_t chunk);
+int llda_label_metrics(const llda_label_args *args, void *stream);
+
+/* Label SETS from per-label thresholds (additive to ABI 22): document d predicts label k when score[d][k] >= thr[k],
+ * an IEEE compare (so a NaN threshold means "never", and -0 >= +0).
+ *   score [D][ld] doubles, ld >= K; thr [K] doubles; truth [D][K] uint8 or NULL; columns below `first` are never predicted, never
+ *   counted and, like the padding bits of a mask row, always 0.  A column first .. K-1 whose thr is not a NaN is ELIGIBLE.
+ *   mask    [D][W] uint32, W = (K + 31) / 32: bit k & 31 of word k >> 5 = label k is predicted
+ *   n_pred  [D] int32: the number of predicted labels
+ *   at_least_one = 1: a document whose mask would be empty predicts its best eligible label: the first by (score descending as IEEE
+ *           values, topic id ascending) -- the order of llda_rank_labels.  That bit counts as predicted in every output.  (No eligible
+ *           column: the mask stays empty.)
+ *   A document with a NaN score in an eligible column predicts nothing, with or without at_least_one, and gets n_pred = -1.
+ *   With truth: n_hit [D] int32 = predicted and true, n_true [D] int32 = true labels among first .. K-1, and tp, fp, fn [K] int64:
+ *   the documents that predict and carry / predict and do not carry / carry and do not predict label k.  tp, fp and fn are ADDED to
+ *   (integer atomics: the sums do not depend on the order): THE CALLER ZEROES THEM, and may accumulate several calls.
+ * Every output pointer may be NULL on its own; without truth n_hit, n_true, tp, fp and fn are not written.  D == 0 is a no-op.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG, before anything touches HIP: a NULL args; a struct_bytes other than
+ * sizeof(llda_sets_args); first outside 0 .. K; ld < K; D < 0 or D x ld beyond an int64; at_least_one other than 0 and 1; and with
+ * D > 0: a NULL score or thr, a misaligned pointer (8 bytes: score, thr, tp, fp, fn; 4: mask, n_pred, n_hit, n_true). */
+typedef struct llda_sets_args {
+    uint32_t struct_bytes;       /* sizeof(llda_sets_args)                                       */
+    int32_t  K, first, at_least_one;
+    const double  *score;        /* [dev] [D][ld]                                                */
+    const double  *thr;          /* [dev] [K]                                                    */
+    const uint8_t *truth;        /* [dev] [D][K] or NULL                                         */
+    int64_t  D, ld;
+    uint32_t *mask;              /* [dev] [D][(K + 31) / 32] or NULL                             */
+    int32_t  *n_pred;            /* [dev] [D] or NULL                                            */
+    int32_t  *n_hit;             /* [dev] [D] or NULL                                            */
+    int32_t  *n_true;            /* [dev] [D] or NULL                                            */
+    int64_t  *tp;                /* [dev] [K] or NULL, added to                                  */
+    int64_t  *fp;                /* [dev] [K] or NULL, added to                                  */
+    int64_t  *fn;                /* [dev] [K] or NULL, added to                                  */
+} llda_sets_args;
+int llda_sets_struct_bytes(void);
+int llda_label_sets(const llda_sets_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

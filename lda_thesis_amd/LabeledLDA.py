@@ -692,6 +692,62 @@ class LabeledLDA(object):
         votes = self._knn_votes(newdocs, it, thinning, k, measure, seed, stream_id)
         return ranking.metrics(ranking.rank_labels(votes, binary_yreal(labels, self.labelmap), first=1, top_n=0))
 
+    # ---- label-wise evaluation and tuned label sets (new; labelwise.py) ----
+    def _label_result(self, newdocs, labels, it, thinning, seed, stream_id, order=False):
+        from . import labelwise
+        from .evaluate import binary_yreal
+        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        return labelwise.label_metrics(th, binary_yreal(labels, self.labelmap), first=1, order=order)
+
+    def label_report(self, newdocs, labels, it, thinning, seed=None, stream_id=None):
+        """Which labels does the model predict well?  Folds ``newdocs`` in as ``score_test`` does and ranks, for every label but
+        'root', the documents by that label's load (llda_label_metrics): dict(table=[(name, support, auc, f1, threshold), ...] in
+        label order, plus ``labelwise.macro``'s macro_auc, macro_f1, n_labels, skipped).  auc is the standard label-wise AUC (nan
+        for a label that no or every document carries), f1 the best F1 any threshold reaches and threshold the load that reaches it.
+        Every rank does the whole call: no collective."""
+        from . import labelwise
+        res = self._label_result(newdocs, labels, it, thinning, seed, stream_id)
+        out = labelwise.macro(res)
+        h = res.host()
+        names = list(self.labelmap.keys())[1:]
+        out["table"] = [(names[i], int(h["n_pos"][i]), float(h["auc"][i]), float(h["f1"][i]), float(h["thr"][i])) for i in range(len(names))]
+        return out
+
+    def tune_thresholds(self, valdocs, vallabels, it, thinning, seed=None, stream_id=None):
+        """SCut: for every label the load threshold that maximises its F1 over the validation documents (folded in as ``score_test``
+        folds them in).  Stores and returns ``self.label_thresholds``: K doubles, NaN -- never predicted -- for 'root' and for labels
+        without a positive validation document.  Every rank does the whole call: no collective."""
+        from . import labelwise
+        self.label_thresholds = labelwise.thresholds(self._label_result(valdocs, vallabels, it, thinning, seed, stream_id))
+        return self.label_thresholds
+
+    def _tuned(self):
+        thr = getattr(self, "label_thresholds", None)
+        if thr is None:
+            raise ValueError("no thresholds: call tune_thresholds(valdocs, vallabels, it, thinning) first")
+        return thr
+
+    def predict_sets(self, newdocs, it, thinning, at_least_one=True, seed=None, stream_id=None):
+        """One list of label names per document, in label-index order: the labels whose load reaches their tuned threshold
+        (llda_label_sets) instead of always n labels.  at_least_one: a document that reaches none gets its best label among those
+        with a threshold.  Only the bit masks come back to the host."""
+        from . import labelwise
+        thr = self._tuned()
+        if len(newdocs) == 0:
+            return []
+        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        names = np.array(list(self.labelmap.keys()))
+        return [list(names[row]) for row in labelwise.label_sets(th, thr, None, first=1, at_least_one=at_least_one).sets()]
+
+    def score_test_sets(self, newdocs, labels, it, thinning, at_least_one=True, seed=None, stream_id=None):
+        """Fold ``newdocs`` in, predict label sets with the tuned thresholds and score them against ``labels``:
+        dict(micro_f1, macro_f1, example_f1, labels_scored, docs_scored) (``labelwise.set_scores``)."""
+        from . import labelwise
+        from .evaluate import binary_yreal
+        thr = self._tuned()
+        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        return dict(labelwise.label_sets(th, thr, binary_yreal(labels, self.labelmap), first=1, at_least_one=at_least_one).scores())
+
     # ---- pickling: pull the device state to the host (evaluate_LabeledLDA.py:142-145 pickles the model)
     def __getstate__(self):
         self.ph_hat, self.th_hat                      # bring the running means to the host

@@ -105,6 +105,21 @@ class LldaNearestArgs(ctypes.Structure):
                 ("top_val", _c_p), ("n_nan", _c_p), ("scratch", _c_p), ("scratch_bytes", _c_i64)]
 
 
+class LldaLabelArgs(ctypes.Structure):
+    """struct llda_label_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("first", _c_i32), ("n_labels", _c_i32), ("chunk", _c_i32), ("reserved", _c_i32),
+                ("score", _c_p), ("truth", _c_p), ("D", _c_i64), ("ld", _c_i64), ("n_pos", _c_p), ("n_thr", _c_p), ("auc_num", _c_p),
+                ("auc", _c_p), ("thr_tp", _c_p), ("thr_fp", _c_p), ("f1", _c_p), ("thr", _c_p), ("flags", _c_p), ("order", _c_p),
+                ("scratch", _c_p), ("scratch_bytes", _c_i64)]
+
+
+class LldaSetsArgs(ctypes.Structure):
+    """struct llda_sets_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("first", _c_i32), ("at_least_one", _c_i32), ("score", _c_p), ("thr", _c_p),
+                ("truth", _c_p), ("D", _c_i64), ("ld", _c_i64), ("mask", _c_p), ("n_pred", _c_p), ("n_hit", _c_p), ("n_true", _c_p),
+                ("tp", _c_p), ("fp", _c_p), ("fn", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -112,7 +127,8 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
            "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik", "llda_attribute",
            "llda_leftright_struct_bytes", "llda_left_to_right",
-           "llda_nearest_struct_bytes", "llda_nearest_scratch_bytes", "llda_nearest_rows")
+           "llda_nearest_struct_bytes", "llda_nearest_scratch_bytes", "llda_nearest_rows",
+           "llda_label_struct_bytes", "llda_label_scratch_bytes", "llda_label_metrics", "llda_sets_struct_bytes", "llda_label_sets")
 
 _LIB = None
 
@@ -204,6 +220,16 @@ def lib():
     L.llda_nearest_scratch_bytes.argtypes = [_c_i64, _c_i64, _c_i32, _c_i32]
     L.llda_nearest_rows.restype = ctypes.c_int
     L.llda_nearest_rows.argtypes = [ctypes.POINTER(LldaNearestArgs), _c_p]
+    L.llda_label_struct_bytes.restype = ctypes.c_int
+    L.llda_label_struct_bytes.argtypes = []
+    L.llda_label_scratch_bytes.restype = _c_i64
+    L.llda_label_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
+    L.llda_label_metrics.restype = ctypes.c_int
+    L.llda_label_metrics.argtypes = [ctypes.POINTER(LldaLabelArgs), _c_p]
+    L.llda_sets_struct_bytes.restype = ctypes.c_int
+    L.llda_sets_struct_bytes.argtypes = []
+    L.llda_label_sets.restype = ctypes.c_int
+    L.llda_label_sets.argtypes = [ctypes.POINTER(LldaSetsArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -221,6 +247,9 @@ def lib():
     if L.llda_nearest_struct_bytes() != ctypes.sizeof(LldaNearestArgs):
         raise NativeError("LldaNearestArgs: binding has %d bytes, the library %d" % (ctypes.sizeof(LldaNearestArgs),
                                                                                      L.llda_nearest_struct_bytes()))
+    for name, struct, size in (("LldaLabelArgs", LldaLabelArgs, L.llda_label_struct_bytes()), ("LldaSetsArgs", LldaSetsArgs, L.llda_sets_struct_bytes())):
+        if size != ctypes.sizeof(struct):
+            raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
     return L
 
@@ -499,6 +528,42 @@ def nearest_rows(a, b, Q, D, L, n, scratch, *, lda=None, ldb=None, row_base=0, e
                            int(a.stride(0) if lda is None else lda), int(b.stride(0) if ldb is None else ldb), int(row_base),
                            _ptr(top_idx), _ptr(top_val), _ptr(n_nan), _ptr(scratch), int(scratch.numel() * scratch.element_size()))
     _launch(scratch, lib().llda_nearest_rows, "llda_nearest_rows", ctypes.byref(args))
+
+
+LABEL_CHUNK = 4096            # LLDA_LABEL_CHUNK: pairs one workgroup of llda_label_metrics sorts in LDS
+LABEL_TEST_CHUNK = 256        # LLDA_LABEL_TEST_CHUNK: the one other value of llda_label_args.chunk
+LABEL_MAX_D = 1 << 30         # LLDA_LABEL_MAX_D
+
+
+def label_scratch_bytes(D, n_labels, chunk=0):
+    """llda_label_scratch_bytes: bytes of work space llda_label_metrics needs (host only)."""
+    r = int(lib().llda_label_scratch_bytes(int(D), int(n_labels), int(chunk)))
+    if r < 0:
+        check(r, "llda_label_scratch_bytes(D=%d, n_labels=%d, chunk=%d)" % (D, n_labels, chunk))
+    return r
+
+
+def label_metrics(score, truth, D, K, first, n_labels, scratch, *, ld=None, chunk=0, n_pos=None, n_thr=None, auc_num=None, auc=None,
+                  thr_tp=None, thr_fp=None, f1=None, thr=None, flags=None, order=None):
+    """llda_label_metrics on the current torch stream: score (D, ld) float64 in reference topic order, truth (D, K) uint8; the
+    outputs (n_labels,) int64 / float64 / int32 and order (n_labels, D) int32, each may be None; scratch = a uint8 tensor of
+    label_scratch_bytes(D, n_labels, chunk) bytes."""
+    a = LldaLabelArgs(ctypes.sizeof(LldaLabelArgs), int(K), int(first), int(n_labels), int(chunk), 0, _ptr(score), _ptr(truth), int(D),
+                      int(score.stride(0) if ld is None else ld), _ptr(n_pos), _ptr(n_thr), _ptr(auc_num), _ptr(auc), _ptr(thr_tp),
+                      _ptr(thr_fp), _ptr(f1), _ptr(thr), _ptr(flags), _ptr(order), _ptr(scratch),
+                      int(scratch.numel() * scratch.element_size()))
+    _launch(score, lib().llda_label_metrics, "llda_label_metrics", ctypes.byref(a))
+
+
+def label_sets(score, thr, truth, D, K, first, at_least_one, *, ld=None, mask=None, n_pred=None, n_hit=None, n_true=None, tp=None,
+               fp=None, fn=None):
+    """llda_label_sets on the current torch stream: score (D, ld) float64, thr (K,) float64, truth (D, K) uint8 or None; mask
+    (D, (K + 31) // 32) int32 bit words, n_pred, n_hit, n_true (D,) int32, tp, fp, fn (K,) int64 ADDED to (zero them); each may be
+    None."""
+    a = LldaSetsArgs(ctypes.sizeof(LldaSetsArgs), int(K), int(first), 1 if at_least_one else 0, _ptr(score), _ptr(thr), _ptr(truth),
+                     int(D), int(score.stride(0) if ld is None else ld), _ptr(mask), _ptr(n_pred), _ptr(n_hit), _ptr(n_true), _ptr(tp),
+                     _ptr(fp), _ptr(fn))
+    _launch(score, lib().llda_label_sets, "llda_label_sets", ctypes.byref(a))
 
 
 def loglik(doc_off, word, lab_mask, n_dk, n_kw, n_k, D, V, K, alpha, beta, out_doc):

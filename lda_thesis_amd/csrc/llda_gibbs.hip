@@ -45,6 +45,8 @@
 //   kernel_attr.hpp     llda_attr_wave_kernel, _lds_kernel, _group_kernel           per-word label shares, credit and the EM fold-in
 //   kernel_leftright.hpp llda_leftright_kernel   left-to-right estimate of a document's likelihood: one particle per wavefront
 //   kernel_nearest.hpp  llda_nearest_kernel, llda_nearest_merge_kernel   the n best rows of b per row of a: tiled fp64 product, selection in its epilogue
+//   kernel_label.hpp    llda_label_keys / _sort / _merge / _walk kernels   the documents of every label ranked: chunk sort in LDS, merge levels, one walk
+//                       llda_label_sets_kernel   per-label thresholds applied to every document: masks by ballot, tp / fp / fn
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -79,6 +81,7 @@
 #include "kernel_attr.hpp"
 #include "kernel_leftright.hpp"
 #include "kernel_nearest.hpp"
+#include "kernel_label.hpp"
 
 namespace {
 
@@ -1066,6 +1069,88 @@ int llda_nearest_rows(const llda_nearest_args *a, void *stream)
         else hipLaunchKernelGGL(llda_nearest_kernel<false>, grid, dim3(256), 0, st, P);
     }
     hipLaunchKernelGGL(llda_nearest_merge_kernel, dim3((unsigned)((a->Q + 63) / 64)), dim3(64), 0, st, P);
+    return launched();
+}
+
+int llda_label_struct_bytes(void) { return (int)sizeof(llda_label_args); }
+int llda_sets_struct_bytes(void) { return (int)sizeof(llda_sets_args); }
+
+static int64_t label_chunk(int32_t chunk) { return chunk == 0 ? LABEL_CHUNK : chunk == LABEL_TEST_CHUNK ? LABEL_TEST_CHUNK : 0; }
+
+int64_t llda_label_scratch_bytes(int64_t D, int32_t n_labels, int32_t chunk)
+{
+    const int64_t C = label_chunk(chunk);
+    if (D < 0 || D > LLDA_LABEL_MAX_D || n_labels < 0 || n_labels > LLDA_MAX_K || C == 0) return LLDA_E_BAD_ARG;
+    const int64_t Dp = (D + C - 1) / C * C;               // (Dp <= 2^30, n_labels < 2^13: the product stays below 2^48)
+    return 24 * Dp * n_labels + 16;                       // (never 0: a caller's allocation always has an address)
+}
+
+int llda_label_metrics(const llda_label_args *a, void *stream)
+{
+    static_assert(LABEL_CHUNK == LLDA_LABEL_CHUNK && LABEL_TEST_CHUNK == LLDA_LABEL_TEST_CHUNK, "kernel_label.hpp restates the header");
+    static_assert(LABEL_CHUNK % LABEL_TILE == 0 && LABEL_TILE == 8 * LABEL_WALK_NT && LABEL_TEST_CHUNK % 64 == 0, "label tiles");
+    if (!a || a->struct_bytes != sizeof(llda_label_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->first < 0 || a->n_labels < 0 || a->first > a->K - a->n_labels || a->ld < a->K) return LLDA_E_BAD_ARG;
+    if (a->D < 0 || a->D > LLDA_LABEL_MAX_D || label_chunk(a->chunk) == 0) return LLDA_E_BAD_ARG;
+    if (a->D == 0 || a->n_labels == 0) return LLDA_OK;
+    if (!a->score || !a->truth || !a->scratch || a->D > INT64_MAX / a->ld) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->score, a->n_pos, a->n_thr, a->auc_num, a->auc, a->thr_tp, a->thr_fp, a->f1, a->thr) || misaligned(7, a->scratch)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->flags, a->order)) return LLDA_E_BAD_ARG;
+    const int64_t need = llda_label_scratch_bytes(a->D, a->n_labels, a->chunk);
+    if (need < 0 || a->scratch_bytes < need) return LLDA_E_BAD_ARG;
+    const int64_t C = label_chunk(a->chunk), Dp = (a->D + C - 1) / C * C, n = Dp * a->n_labels;
+    LabelParams P;
+    memset(&P, 0, sizeof P);
+    P.score = a->score; P.truth = a->truth; P.D = a->D; P.ld = a->ld; P.Dp = Dp;
+    P.K = a->K; P.first = a->first; P.n_labels = a->n_labels;
+    P.key_a = static_cast<uint64_t *>(a->scratch);
+    P.key_b = P.key_a + n;
+    P.pay_a = reinterpret_cast<uint32_t *>(P.key_b + n);
+    P.pay_b = P.pay_a + n;
+    P.n_pos = a->n_pos; P.n_thr = a->n_thr; P.auc_num = a->auc_num; P.auc = a->auc; P.thr_tp = a->thr_tp; P.thr_fp = a->thr_fp;
+    P.f1 = a->f1; P.thr = a->thr; P.flags = a->flags; P.order = a->order;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned L = (unsigned)a->n_labels;
+    hipLaunchKernelGGL(llda_label_keys_kernel, dim3((unsigned)(Dp / 64), (L + 63) / 64), dim3(256), 0, st, P);
+    const bool small = C == LABEL_TEST_CHUNK;
+    if (small) hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Dp / C), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, P);
+    else hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_CHUNK>, dim3((unsigned)(Dp / C), L), dim3(LABEL_CHUNK / 8), 0, st, P);
+    int flip = 0;
+    for (int64_t R = C; R < Dp; R *= 2, flip ^= 1) {
+        P.run = R;
+        if (small) hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Dp / LABEL_TEST_CHUNK), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, P, flip);
+        else hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TILE>, dim3((unsigned)(Dp / LABEL_TILE), L), dim3(LABEL_TILE / 8), 0, st, P, flip);
+    }
+    P.key_sorted = flip ? P.key_b : P.key_a;
+    P.pay_sorted = flip ? P.pay_b : P.pay_a;
+    hipLaunchKernelGGL(llda_label_walk_kernel, dim3(L), dim3(LABEL_WALK_NT), 0, st, P);
+    return launched();
+}
+
+int llda_label_sets(const llda_sets_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_sets_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->first < 0 || a->first > a->K || a->ld < a->K || a->D < 0 || a->D > INT64_MAX / a->ld) return LLDA_E_BAD_ARG;
+    if (a->at_least_one != 0 && a->at_least_one != 1) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->score || !a->thr) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->score, a->thr, a->tp, a->fp, a->fn) || misaligned(3, a->mask, a->n_pred, a->n_hit, a->n_true)) return LLDA_E_BAD_ARG;
+    SetsParams P;
+    memset(&P, 0, sizeof P);
+    P.score = a->score; P.thr = a->thr; P.truth = a->truth; P.D = a->D; P.ld = a->ld;
+    P.K = a->K; P.first = a->first; P.at_least_one = a->at_least_one; P.W = (a->K + 31) / 32;
+    P.mask = a->mask; P.n_pred = a->n_pred; P.n_hit = a->n_hit; P.n_true = a->n_true;
+    P.tp = reinterpret_cast<unsigned long long *>(a->tp); P.fp = reinterpret_cast<unsigned long long *>(a->fp);
+    P.fn = reinterpret_cast<unsigned long long *>(a->fn);
+    // LDS: whole ballots of mask words per wavefront, and with truth three counters per label (K <= 7688: at most 100 KB)
+    const size_t lds = sizeof(uint32_t) * ((size_t)SETS_WAVES * ((a->K + 63) / 64 * 2) + (a->truth ? 3 * (size_t)a->K : 0));
+    const int rl = allow_lds(llda_label_sets_kernel, lds);
+    if (rl) return rl;
+    const int64_t rounds = (a->D + SETS_WAVES - 1) / SETS_WAVES;
+    // every workgroup flushes K counters: a few workgroups per compute unit, each with many documents
+    hipLaunchKernelGGL(llda_label_sets_kernel, dim3((unsigned)(rounds < 1024 ? rounds : 1024)), dim3(SETS_WAVES * 64), lds, (hipStream_t)stream, P);
     return launched();
 }
 

@@ -45,7 +45,47 @@ def build_parser():
                       "document (Hellinger affinity of the loads; llda_nearest_rows)")
     p.add_option("--similar-labels", dest="similar_labels", type="int", default=0, metavar="N",
                  help="after the report: every label with its N nearest labels by word distribution (llda_nearest_rows)")
+    p.add_option("--label-report", action="store_true", dest="label_report", default=False,
+                 help="after the report: label-wise evaluation of the test documents (llda_label_metrics): macro-averaged AUC and "
+                      "best F1 over the labels, and the ten best and ten worst labels by AUC")
+    p.add_option("--label-sets", action="store_true", dest="label_sets", default=False,
+                 help="after the report: per-label thresholds tuned for F1 on the even-indexed documents of the test split, then "
+                      "micro / macro / example-based F1 of the predicted label sets on its odd-indexed documents (llda_label_sets)")
     return p
+
+
+def report_labels(model, test, it, thinning):
+    """macro figures over the labels and the ten best / ten worst labels by AUC (LabeledLDA.label_report)"""
+    known = set(model.vocab)
+    r = model.label_report([[x for x in doc if x in known] for doc in test[0]], test[1], it, thinning)
+    print("-----------------------------------")
+    print("Label-wise evaluation over %d labels (%d without a positive or a negative test document):" % (r["n_labels"], r["skipped"]))
+    print("AUC ROC (macro over labels):  ", r["macro_auc"])
+    print("best F1 (macro over labels):  ", r["macro_f1"])
+    rows = sorted((x for x in r["table"] if x[2] == x[2]), key=lambda x: (-x[2], x[0]))
+    for title, part in (("best", rows[:10]), ("worst", rows[::-1][:10])):
+        print("ten %s labels by AUC (label, support, AUC, best F1, threshold):" % title)
+        for name, support, auc, f1, thr in part:
+            print("  %-24s %6d  %.4f  %.4f  %.6g" % (name, support, auc, f1, thr))
+    return r
+
+
+def report_label_sets(model, test, it, thinning):
+    """thresholds tuned on the even-indexed test documents, label sets scored on the odd-indexed ones"""
+    known = set(model.vocab)
+    docs = [[x for x in doc if x in known] for doc in test[0]]
+    labels = list(test[1])
+    thr = model.tune_thresholds(docs[0::2], labels[0::2], it, thinning)
+    print("-----------------------------------")
+    print("Label sets: %d thresholds tuned on %d documents, scored on %d:" % (int((~np.isnan(thr)).sum()), len(docs[0::2]), len(docs[1::2])))
+    if not docs[1::2]:
+        print("  no document to score")
+        return None
+    r = model.score_test_sets(docs[1::2], labels[1::2], it, thinning)
+    print("F1 (micro):              ", r["micro_f1"])
+    print("F1 (macro over labels):  ", r["macro_f1"])
+    print("F1 (example-based):      ", r["example_f1"])
+    return r
 
 
 def report_knn(model, test, it, thinning, k):
@@ -197,6 +237,10 @@ def main(argv=None):
         report_knn(model, test, opt.it, opt.thinning, opt.knn)
     if opt.similar_labels:
         report_similar_labels(model, opt.similar_labels)
+    if opt.label_report:
+        report_labels(model, test, opt.it, opt.thinning)
+    if opt.label_sets:
+        report_label_sets(model, test, opt.it, opt.thinning)
 
 
 if __name__ == "__main__":
