@@ -253,55 +253,93 @@ __device__ __forceinline__ uint64_t quad_draw(const q_v32f &xv, const q_v2f (&pa
     return unsure;
 }
 
-// Tier 1 in the quad layout, for the wavefront iterations in which tier 0 is unsure about some document: the decision from
-// unnormalised fp64 prefix sums with the margin 2^-40 of the total (draw_tiers.hpp, cold_tiers_acc: the same test on a different
-// association order -- the bound there, 254 u < 2^-44, grows by the 16 more additions of a 32-slot chain).  All four documents at once;
-// xv = the row minus the site's own count, exact in fp32.  Returns the ballot of the lanes that are STILL not sure; zn as quad_draw.
-template <int LB, bool PAD = false>
-__device__ __forceinline__ uint64_t quad_tier1(const q_v32f &xv, const int (*s_ndk)[QNT][4], const int *s_nk0, int tid, int lq, double u,
-                                               double alpha, double beta, double vbeta, double margin_rel, uint32_t vm, int &zn)
+// Tier 1 of the quad layout: the decision from unnormalised fp64 prefix sums with the margin 2^-40 of the total, the test
+// of cold_tiers_acc (draw_tiers.hpp) -- for ONE document, on all 64 lanes of the wavefront.  Tier 0 is unsure about 0.2 % of the sites
+// and a wavefront walks 64 / LPD documents, so almost every entry is about one of them: played in the documents' own lanes (LPD lanes x
+// 32 slots, all documents at once), three quarters and more of the fp64 work went to documents that were decided already.  Here lane s
+// takes the n = KP / 64 (8, 4, 2) consecutive positions s n .. s n + n - 1 of the document's draw order (quad_doc_map.hpp: quad lane,
+// then chain A / B, then element a -- the order of the standard lanes and slots), reads
+//   - its n counts of the word's row from the 16-bit image once more (2 n contiguous bytes of one piece: ONE load per lane, issued
+//     first; the image is this sweep's snapshot and the wavefront fetched the row an iteration ago), minus the site's own count f in
+//     the one lane and slot that hold the old position zo, taken from the integer before the conversion;
+//   - n_dk and the sweep-start n_dk of the slot from the LDS of the document's lanes (tbase = thread of its quad lane 0), n_k from s_nk0;
+// and the prefix sums run over the lane's n terms, then over the 64 lanes.  PAD: a position without a topic contributes 0.0.
+// Error, with u = 2^-53.  A term is the expression of cold_tiers_acc: 1 / den within 2^-50 = 8 u (fp32 seed, two Newton steps) and three
+// roundings more, 11 u of the term.  A prefix takes at most n - 1 <= 7 additions in the lane and six scan steps (a 32-slot chain in 16
+// lanes took 31 + 4): a lane's prefix is within 18 u, the scanned sums and the total within 24 u of the total, the target
+// fl(uniform * tot) - prev and its bounds within 24 + 1 + 24 + 3 = 52 u, a compared difference within 70 u < 2^-46 of the total -- inside
+// the 254 u < 2^-44 the margin 2^-40 was set against (draw_tiers.hpp).
+// Another summation order than before, so WHICH handful of sites per 10^10 go on to the exact tier may differ; a decided draw may not.
+// Out of line, with the arguments of quad_cold (w, f, zo, d = word, frequency, old position and document of the site, ra / rb = its random
+// bits: all wavefront uniform): inlined, its scalar registers are taken from the site loop's (the commit's log pointer was loaded again
+// every iteration).  Returns position | rho << 9 (as quad_draw's zn), or -1: the document is STILL not sure.
+template <int LB, bool PAD>
+__device__ __noinline__ int quad_tier1_doc(const int (*s_ndk)[QNT][4], const int *s_nk0, int tbase, int w, int f, int zo, uint32_t ra, uint32_t rb,
+                                           int lane, int64_t d, const KParams *P)
 {
-    double W[QT];
+    typedef QuadGeo<LB> Geo;
+    constexpr int N = quad_doc_terms(LB);
+    static_assert(N * 64 == Geo::KP, "64 lanes x n terms are the positions of a document");
+    const int o0 = quad_doc_order(LB, lane, 0);                   // (the n positions of a lane share quad lane, chain and 16-byte piece)
+    const int lqd = quad_doc_lane(o0);
+    uint32_t xr[(N + 1) / 2];                                     // the lane's n 16-bit counts
+    {
+        const LLDA_GLOBAL char *q = (const LLDA_GLOBAL char *)P->n_kw16 + (((uint32_t)w << (Geo::IS + 3)) + (uint32_t)quad_doc_image_byte(LB, o0));
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+        if constexpr (N == 8) {
+            const v4u r = *(const LLDA_GLOBAL v4u *)q;
+            xr[0] = r.x; xr[1] = r.y; xr[2] = r.z; xr[3] = r.w;
+        } else if constexpr (N == 4) {
+            const v2u r = *(const LLDA_GLOBAL v2u *)q;
+            xr[0] = r.x; xr[1] = r.y;
+        } else {
+            xr[0] = *(const LLDA_GLOBAL uint32_t *)q;
+        }
+    }
+    uint32_t vw = 0xFFFFu;                                        // validity word of the standard lane the positions belong to
+    if constexpr (PAD) vw = P->lab_mask[d * Geo::G + quad_doc_std_lane(o0)];
+    const double alpha = P->alpha, beta = P->beta, vbeta = P->vbeta, u = uniform53(ra, rb);
+    double W[N];
     double run = 0.0;
 #pragma unroll
-    for (int k = 0; k < QT; ++k) {                       // k = position in the draw order of the lane: chain A, then chain B
-        const int e = k >> 4, a = k & 15, i = a >> 2, c = a & 3;
-        const int rho = quad_rho_of(i, e, c);
-        const int w = QLDS(s_ndk, rho, tid);
-        const int nd = w & 0xffff, nk = s_nk0[(i << QuadGeo<LB>::IS) | (lq << 3) | (e << 2) | c] + nd - (int)((uint32_t)w >> 16);
+    for (int t = 0; t < N; ++t) {
+        const int o = o0 + t, rho = quad_doc_rho(o), pos = quad_doc_pos(LB, o);
+        const int c = QLDS(s_ndk, rho, tbase + lqd);
+        const int nd = c & 0xffff, nk = s_nk0[pos] + nd - (int)((uint32_t)c >> 16);
         const double den = (double)nk + vbeta;
         // 1 / den from the fp32 reciprocal (1 ulp) and two Newton steps in fp64: within 2^-50, as cold_tiers_acc's
         double y = (double)__builtin_amdgcn_rcpf((float)den);
         y = __builtin_fma(__builtin_fma(-den, y, 1.0), y, y);
         y = __builtin_fma(__builtin_fma(-den, y, 1.0), y, y);
-        const double ws = ((double)nd + alpha) * (((double)xv[rho] + beta) * y);
-        run = run + (((vm >> k) & 1u) ? ws : 0.0);                // (vm: bit 16 e + a = this position holds a topic)
-        W[k] = run;
+        const int x = (int)((xr[t >> 1] >> (16 * (t & 1))) & 0xffffu) - (pos == zo ? f : 0);
+        const double ws = ((double)nd + alpha) * (((double)x + beta) * y);
+        run = run + (((vw >> quad_doc_std_slot(o)) & 1u) ? ws : 0.0);
+        W[t] = run;
     }
-    constexpr int LPD = QuadGeo<LB>::LPD;
-    const double X = group_scan<LPD>(run, lq);
-    const double tot = bcast_last<LPD>(X, tid & 63);
-    double prev = dpp_f64<DPP_ROW_SHR + 1>(X);                         // (0.0 into the first lane of the row)
-    if constexpr (LB < 4) prev = lq ? prev : 0.0;
-    const double tg = u * tot - prev;
-    const double margin = tot * margin_rel;
+    const double X = group_scan<64>(run, lane);
+    const double tot = bcast_last<64>(X, lane);
+    const double pv = dpp_f64<DPP_WAVE_SHR1>(X);
+    const double tg = u * tot - (lane ? pv : 0.0);
+    const double margin = tot * P->margin_rel;
     const double lo = tg - margin, hi = tg + margin;
     int cnt_lo = 0, cnt_hi = 0;
 #pragma unroll
-    for (int k = 0; k < QT; ++k) {
-        cnt_lo += (W[k] <= lo) ? 1 : 0;
-        cnt_hi += (W[k] <= hi) ? 1 : 0;
+    for (int t = 0; t < N; ++t) {
+        cnt_lo += (W[t] <= lo) ? 1 : 0;
+        cnt_hi += (W[t] <= hi) ? 1 : 0;
     }
-    uint64_t unsure = __ballot((cnt_lo != cnt_hi) || !(tot > 0.0) || !(margin < tot));
-    // position of chain index cnt_lo: e = k >> 4, i = (k >> 2) & 3, c = k & 3
-    const uint32_t k = (uint32_t)cnt_lo;
-    const uint32_t i_ = (k >> 2) & 3u, e_ = (k >> 4) & 1u, c_ = k & 3u;
-    const uint32_t p = (i_ << QuadGeo<LB>::IS) | ((uint32_t)lq << 3) | (e_ << 2) | c_ | ((8u * i_ + 2u * c_ + e_) << 9) | ((uint32_t)lq << QK_LANE);
-    uint32_t key = cnt_lo >= QT ? QUAD_KEY_NONE<LB> : p;
-    key = quad_min_key<LB>(key);
-    zn = (int)(key & QK_ZN);
-    if constexpr (PAD) unsure |= __ballot(key == QUAD_KEY_NONE<LB>);           // (see quad_draw)
-    return unsure;
+    bool still = __ballot((cnt_lo != cnt_hi) || !(tot > 0.0) || !(margin < tot)) != 0;
+    // the first lane with a prefix above lo names the position; none: the last one (PAD: it holds no topic -- not sure, see quad_draw)
+    const uint64_t hit = __ballot(cnt_lo < N);
+    int o = Geo::KP - 1;
+    if (hit) {
+        const int sl = __builtin_ctzll(hit);
+        o = quad_doc_order(LB, sl, __builtin_amdgcn_readlane(cnt_lo, sl));
+    } else if constexpr (PAD) {
+        still = true;
+    }
+    return still ? -1 : quad_doc_pos(LB, o) | quad_doc_rho(o) << 9;
 }
 
 struct QuadSite { int v, f, zo, c, zn, lo, so; uint8_t w; };  // (lo, so) = quad lane and slot number of zo; w = flag of the word's row (0: wide)
@@ -318,9 +356,11 @@ static_assert(offsetof(QuadDocLds, pa) == sizeof(int) * QT * QNT && sizeof(int) 
               "the factor of a slot is an immediate offset away from its count");
 
 // -DQUAD_PROFILE (tools/quad_phase_profile.py; never in a production build: llda_build_info reports it): wavefront 0 of workgroup 0
-// stamps the shader clock at the phase boundaries of every site and adds the differences up in status[8 + phase]
+// stamps the shader clock at the phase boundaries of every site and adds the differences up in status[8 + phase]; an iteration that
+// enters the cold tiers is stamped at the end of the rare block too (status[15]: from the end of phase 1) and counted (status[17])
 #ifdef QUAD_PROFILE
-#define QP_DECL uint32_t qp_t = 0, qp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define QP_DECL uint32_t qp_t = 0, qp_entries = 0, qp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define QP_ENTRY() do { QP_MARK(7); ++qp_entries; } while (0)
 #define QP_START() do { __builtin_amdgcn_sched_barrier(0); qp_t = (uint32_t)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define QP_MARK(k) do { __builtin_amdgcn_sched_barrier(0); const uint32_t qp_n = (uint32_t)__builtin_amdgcn_s_memtime(); \
                         qp_acc[k] += qp_n - qp_t; qp_t = qp_n; __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -328,6 +368,7 @@ static_assert(offsetof(QuadDocLds, pa) == sizeof(int) * QT * QNT && sizeof(int) 
 #define QP_DECL
 #define QP_START()
 #define QP_MARK(k)
+#define QP_ENTRY()
 #endif
 
 // REC: {word, freq, csc_pos} of a site come as one 16-byte record (llda_sweep_args.site_rec; always for LB < 4)
@@ -608,42 +649,44 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
             LLDA_MARK("cold_check");
             if (__builtin_expect(unsure != 0, 0)) {
                 LLDA_MARK("rare_cold");
-                // tier 1 (fp64, margin 2^-40) right here, in this layout, for all four documents; what IT cannot decide (~1e-9 of the
-                // sites) goes to the exact tier out of line, one document at a time, the whole wavefront playing it in the standard layout
+                // tier 1 (fp64, margin 2^-40) right here, one document at a time on all 64 lanes (usually ONE trip); what IT cannot
+                // decide (~1e-9 of the sites) goes to the exact tier out of line, the whole wavefront playing it in the standard layout
                 const int holder = (n >> 1) & (LPD - 1);
                 const uint32_t ra_l = (n & 1) ? r2 : r0, rb_l = (n & 1) ? r3 : r1;
                 const int bp_h = (gbase | holder) << 2;
                 const uint32_t ra = (uint32_t)__builtin_amdgcn_ds_bpermute(bp_h, (int)ra_l), rb = (uint32_t)__builtin_amdgcn_ds_bpermute(bp_h, (int)rb_l);
-                const uint64_t t0_w = unsure;                          // documents tier 0 was unsure about
+                const uint64_t t0_w = unsure;                          // documents tier 0 was unsure about (of those that have the site)
                 if (lq == 0 && ((t0_w >> gbase) & Geo::GM) && P.status) atomicAdd(P.status + 1, 1);   // statistics
-                int z1;
-                // (skips tier 1: a document whose row was read as int32 -- a count of 2^24 or more is not exact in xv; HOOKS: a margin >= 1)
-                uint64_t still = ((!HOOKS || P.margin_rel < 1.0 ? quad_tier1<LB, PAD>(xv, s_ndk, s_nk0, tid, lq, uniform53(ra, rb), P.alpha, P.beta, P.vbeta,
-                                                                                  P.margin_rel, vm, z1) : ~0ull) | __ballot(cur.w == 0));
-                if constexpr (!FULL) still &= __ballot(act);
-                const bool mine0 = ((t0_w >> gbase) & Geo::GM) != 0;
-                zn = mine0 ? z1 : zn;
+                // (skips tier 1: a document whose row was read as int32 -- the 16-bit image does not hold it; HOOKS: a margin >= 1)
+                const uint64_t wide_w = __ballot(cur.w == 0);
+                const bool tier1 = !HOOKS || P.margin_rel < 1.0;
                 uint32_t rows = 0;
 #pragma unroll
-                for (int r = 0; r < Geo::DPW; ++r)
-                    rows |= (((t0_w >> (LPD * r)) & Geo::GM) && ((still >> (LPD * r)) & Geo::GM)) ? (1u << r) : 0u;
+                for (int r = 0; r < Geo::DPW; ++r) rows |= ((t0_w >> (LPD * r)) & Geo::GM) ? (1u << r) : 0u;
                 rows = (uint32_t)__builtin_amdgcn_readfirstlane((int)rows);
-                while (__builtin_expect(rows != 0, 0)) {
+                while (__builtin_expect(rows != 0, 1)) {
                     const int r = __builtin_ctz(rows);
                     rows &= rows - 1;
                     const int src = r * LPD;
-                    const int zo_r = __builtin_amdgcn_readlane(zo, src);
-                    int zc = quad_cold<LB, PAD>(s_ndk, s_nk0, (tid & 64) + src, __builtin_amdgcn_readlane(cur.v, src),
-                                       __builtin_amdgcn_readlane(f, src), zo_r, (uint32_t)__builtin_amdgcn_readlane((int)ra, src),
-                                       (uint32_t)__builtin_amdgcn_readlane((int)rb, src), lane,
-                                       (int64_t)__builtin_amdgcn_readlane((int)d, src),          // (llda_sweep: D < 2^31)
-                                       (const KParams *)__builtin_amdgcn_kernarg_segment_ptr());
-                    if (__builtin_expect(zc < 0, 0)) {
-                        zc = zo_r;
-                        if (lane == 0 && P.status) atomicOr(P.status, 1);   // no topic with positive probability
+                    const int zo_r = __builtin_amdgcn_readlane(zo, src), w_r = __builtin_amdgcn_readlane(cur.v, src);
+                    const int f_r = __builtin_amdgcn_readlane(f, src);
+                    const uint32_t ra_r = (uint32_t)__builtin_amdgcn_readlane((int)ra, src), rb_r = (uint32_t)__builtin_amdgcn_readlane((int)rb, src);
+                    const int64_t d_r = (int64_t)__builtin_amdgcn_readlane((int)d, src);                 // (llda_sweep: D < 2^31)
+                    const KParams *const Pk = (const KParams *)__builtin_amdgcn_kernarg_segment_ptr();
+                    int zd = -1;
+                    if (tier1 && !((wide_w >> src) & 1))
+                        zd = __builtin_amdgcn_readfirstlane(quad_tier1_doc<LB, PAD>(s_ndk, s_nk0, (tid & 64) + src, w_r, f_r, zo_r, ra_r, rb_r, lane, d_r, Pk));
+                    if (__builtin_expect(zd < 0, 0)) {
+                        int zc = quad_cold<LB, PAD>(s_ndk, s_nk0, (tid & 64) + src, w_r, f_r, zo_r, ra_r, rb_r, lane, d_r, Pk);
+                        if (__builtin_expect(zc < 0, 0)) {
+                            zc = zo_r;
+                            if (lane == 0 && P.status) atomicOr(P.status, 1);   // no topic with positive probability
+                        }
+                        zd = zc | quad_rho<LB>(zc) << 9;
                     }
-                    zn = (row == r) ? (zc | quad_rho<LB>(zc) << 9) : zn;
+                    zn = (row == r) ? zd : zn;
                 }
+                QP_ENTRY();                                            // (an entry: its ticks apart, status[15], and counted, status[17])
             }
             QP_MARK(2);                                                // (cold tiers)
             LLDA_MARK("decode");
@@ -742,6 +785,7 @@ __global__ void __launch_bounds__(QNT, 2) llda_sweep_quad_kernel(const KParams P
 #pragma unroll
             for (int k = 0; k < 8; ++k) atomicAdd(P.status + 8 + k, (int)qp_acc[k]);
             atomicAdd(P.status + 16, maxlen);
+            atomicAdd(P.status + 17, (int)qp_entries);
         }
 #endif
         // document done: fold its n_dk change into the workgroup's n_k accumulator, store the row

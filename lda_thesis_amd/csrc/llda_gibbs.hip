@@ -29,6 +29,7 @@
 //                                                 document): the sparse kernels' answer to a site they cannot decide
 //   kernel_sweep.hpp    llda_sweep_exact_kernel   general kernel, every site through the exact pipeline
 //                       llda_sweep_kernel         tiered kernel, per-document state in LDS (the hot kernel)
+//   quad_doc_map.hpp    quad_tier1_doc's lane-to-position mapping: one document on 64 lanes (constexpr, compiled by a host test too)
 //   kernel_quad.hpp     llda_sweep_quad_kernel    K = 512 dense, 16-bit image: FOUR documents per wavefront (the bench's timed kernel)
 //   kernel_sparse.hpp   llda_sweep_sparse_kernel  one lane per ALLOWED topic for sparse label sets
 //   kernel_batch.hpp    llda_sweep_batch_kernel   one sweep over many independent small problems (CascadeLDA's
@@ -66,6 +67,7 @@
 #include "draw_tiers.hpp"
 #include "exact_generic.hpp"
 #include "kernel_sweep.hpp"
+#include "quad_doc_map.hpp"
 #include "kernel_quad.hpp"
 #include "kernel_sparse.hpp"
 #include "kernel_batch.hpp"
