@@ -405,7 +405,11 @@ int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab
  * separately, as `factor*self.ph_hat + (1/s * cur_ph)` (LabeledLDA.py:144-145) and
  * `m * self.ph + (1-m) * cur_ph` (CascadeLDA.py:432) round -- the caller passes the two coefficients.
  * flags (dev int32[1], OR-ed, may be NULL; phi only) report the guards of LabeledLDA.py:146-153 on `out`:
- *   bit 0 an entry < 0, bit 1 a NaN, bit 2 a word whose column is all zero. */
+ *   bit 0 an entry < 0, bit 1 a NaN, bit 2 a word whose column is all zero.
+ * Padding (positions p < KP with llda_layout.pos_topic[p] < 0): llda_readout_phi uses n_kw, n_k and den at the K positions that
+ * hold a topic only -- the padding may hold anything and changes neither out nor flags.  llda_readout_theta (and llda_loglik)
+ * sum a row of n_dk over all KP positions: the padding of n_dk must be 0, as every producer of counts leaves it, and lab_mask has
+ * no bit there (lane_masks).  Nothing is written outside out[0 .. K*V) / out[0 .. D*K) and flags[0]. */
 #define LLDA_READOUT_NEGATIVE 1
 #define LLDA_READOUT_NAN      2
 #define LLDA_READOUT_NO_LOAD  4

@@ -15,6 +15,7 @@ import pytest
 
 import countref
 from countref import Guarded
+from readoutref import loglik_case, loglik_high_precision
 
 pytestmark = pytest.mark.gpu
 
@@ -516,45 +517,8 @@ def test_pack_image_cols_gathers_and_saturates(bits, K, V):
 U = 2.0 ** -53
 
 
-def loglik_case(K, masks, seed=8):
-    lay = _layout(K)
-    assert not lay.wide
-    D, V = 70, 53
-    rng = np.random.default_rng([seed, K, ("all", "root_and_3", "single").index(masks)])
-    lens = np.resize([0, 1, 90, 5, 17, 2, 33], D)
-    doc_off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
-    S = int(doc_off[-1])
-    labs = np.zeros((D, K), dtype=np.uint8)
-    for d in range(D):
-        if masks == "all":
-            labs[d] = 1
-        elif masks == "single":
-            labs[d, rng.integers(0, K)] = 1
-        else:
-            labs[d, 0] = 1
-            labs[d, 1 + rng.choice(K - 1, 3, replace=False)] = 1
-    word = rng.integers(0, V, S).astype(np.int32)
-    freq = rng.integers(1, 20, S).astype(np.int32)
-    topic = np.concatenate([rng.choice(np.flatnonzero(labs[d]), lens[d]) for d in range(D)]).astype(np.int64)
-    z = lay.topic_pos[topic].astype(np.int32)
-    counts = [_cpu(np.zeros(s, dtype=np.int32)) for s in ((D, lay.KP), (V, lay.KP), (lay.KP,))]
-    _oracle().count_init(_cpu(doc_off), _cpu(word), _cpu(freq), _cpu(z), D, K, *counts)
-    return lay, D, V, lens, doc_off, word, labs, [c.numpy() for c in counts]
-
-
-def loglik_high_precision(lay, doc_off, word, labs, n_dk, n_kw, n_k, V, alpha, beta):
-    """out_doc in long double (64 significant bits on x86: its own error is 2^-11 of a double's)"""
-    ld = np.longdouble
-    tp = lay.topic_pos.astype(np.int64)
-    num = n_dk[:, tp].astype(ld) + labs.astype(ld) * ld(alpha)
-    th = num / num.sum(axis=1)[:, None]
-    ph = (n_kw[:, tp].T.astype(ld) + ld(beta)) / (n_k[tp].astype(ld)[:, None] + ld(V) * ld(beta))
-    out = np.zeros(len(doc_off) - 1, dtype=ld)
-    for d in range(len(out)):
-        w = word[doc_off[d]:doc_off[d + 1]]
-        if len(w):
-            out[d] = -np.log((th[d][:, None] * ph[:, w]).sum(axis=0)).sum()
-    return out
+# loglik_case (which refuses a wide layout here) and loglik_high_precision live in tests/readoutref.py: the test of the wide layouts,
+# tests/test_gpu_readout_direct.py, shares them
 
 
 @pytest.mark.parametrize("masks", ["all", "root_and_3", "single"])
@@ -573,8 +537,8 @@ def test_loglik_per_document_on_the_tuned_layouts(K, masks):
     Together  |device - exact| <= (n (2 KP + 5) + 2 S + n S) u,  asserted with 1 % on top for the second-order terms; the float64
     reference (numpy, the same operations in another order) is within the same bound, so the two float64 values may differ by twice
     as much.  The numpy reference itself uses at most 0.17 of the bound (K = 5, where the n S term of the accumulator dominates) and
-    0.007 - 0.05 of it from K = 40 on; the test prints the device's ratio for every case (pytest -s).  The device's largest ratio
-    has not been recorded yet: no MI355X could be had while this file was written."""
+    0.007 - 0.05 of it from K = 40 on; the test prints the device's ratio for every case (pytest -s).  The device's largest
+    ratios, for this kernel and the wide one, are kept in profiles/readout_loglik_bound.md."""
     import torch
     from lda_thesis_amd import _native as nat
     lay, D, V, lens, doc_off, word, labs, (n_dk, n_kw, n_k) = loglik_case(K, masks)
