@@ -15,7 +15,7 @@ finite (or whose word is unknown) is attributed to nobody and counted in ``bad``
 """
 import numpy as np
 
-from . import _native
+from . import _native, docmodel
 
 MAX_FREQ = _native.HELDOUT_MAX_FREQ
 MAX_TOP = _native.ATTR_MAX_TOP
@@ -63,16 +63,8 @@ def attribute(theta_dev, phi_t_dev, doc_off, word, freq, iters=0, alpha=0.0, top
     import torch
     _native.lib()
     _native.require_device()
-    for name, x in (("theta", theta_dev), ("phi_t", phi_t_dev)):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 2):
-            raise ValueError("%s must be a two-dimensional float64 tensor on the device" % name)
+    theta_dev, phi_t_dev, D, V, K = docmodel.matrices(theta_dev, phi_t_dev)
     dev = theta_dev.device
-    if phi_t_dev.device != dev:
-        raise ValueError("theta and phi_t live on different devices")
-    D, K = int(theta_dev.shape[0]), int(theta_dev.shape[1])
-    V = int(phi_t_dev.shape[0])
-    if int(phi_t_dev.shape[1]) != K:
-        raise ValueError("theta has %d topics, phi_t %d" % (K, int(phi_t_dev.shape[1])))
     iters, top_m, alpha = int(iters), int(top_m), float(alpha)
     if iters < 0:
         raise ValueError("iters must not be negative")
@@ -84,33 +76,8 @@ def attribute(theta_dev, phi_t_dev, doc_off, word, freq, iters=0, alpha=0.0, top
     if set(want) - set(OUTPUTS):
         raise ValueError("want: unknown output %s" % sorted(set(want) - set(OUTPUTS)))
 
-    def rows(x):
-        return x.contiguous() if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < K) else x
-
-    def on_dev(a, dt):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=dev, dtype=dt).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device=dev, dtype=dt)
-
-    theta_dev, phi_t_dev = rows(theta_dev), rows(phi_t_dev)
-    off_h = doc_off.cpu().numpy() if isinstance(doc_off, torch.Tensor) else np.asarray(doc_off, dtype=np.int64)
-    if off_h.shape != (D + 1,) or (D and (int(off_h[0]) < 0 or np.any(np.diff(off_h) < 0))):
-        raise ValueError("doc_off must hold D + 1 = %d ascending offsets" % (D + 1))
-    S = int(off_h[-1]) if D else 0
-    d_off, d_word = on_dev(doc_off, torch.int64), on_dev(word, torch.int32)
-    if int(d_word.numel()) == 0:
-        d_word = torch.zeros((1,), dtype=torch.int32, device=dev)      # (no site at all: the pointer must still be one)
-    if int(d_word.numel()) < S:
-        raise ValueError("word holds %d sites, doc_off asks for %d" % (int(d_word.numel()), S))
-    if S and (int(d_word[:S].min()) < 0 or int(d_word[:S].max()) >= V):
-        raise ValueError("word ids must be in [0, V)")
-    d_freq = None
-    if freq is not None:
-        d_freq = on_dev(freq, torch.int32)
-        if int(d_freq.numel()) < S:
-            raise ValueError("freq holds %d sites, doc_off asks for %d" % (int(d_freq.numel()), S))
-        if S and (int(d_freq[:S].min()) < 0 or int(d_freq[:S].max()) > MAX_FREQ):
-            raise ValueError("frequencies must be in 0 .. 2^23 - 1")
+    _, _, S = docmodel.check_offsets(doc_off, D)
+    d_off, d_word, d_freq = docmodel.stage(dev, doc_off, word, freq, S, V)
     out = {}
     if "theta" in want:
         out["theta"] = torch.empty((D, K), dtype=torch.float64, device=dev)

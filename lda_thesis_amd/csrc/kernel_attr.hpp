@@ -10,11 +10,11 @@ namespace {
 // theta_k = (credit_k + alpha) / sum, a fold-in without random numbers.
 //
 // Arithmetic (fixed by the header, restated in tests/attrref.py): IEEE float64 operations, each rounded on its own (contraction
-// is off in this unit; the two divisions are the correctly rounded ones).  p is the sum of kernel_heldout.hpp -- 64 partials, then
-// the xor tree (heldout_tree) -- and so is the M-step's denominator.  ONE division per site (inv = 1 / p): f * inv is the site's
+// is off in this unit; the two divisions are the correctly rounded ones).  p is the sum of doc_model.hpp -- 64 partials, then
+// the xor tree (doc_tree) -- and so is the M-step's denominator.  ONE division per site (inv = 1 / p): f * inv is the site's
 // weight and t_k * inv its shares.  A site is good when its word is in [0, V) and 2^-960 <= p < inf; any other adds f to bad.
 //
-// Geometry, as in kernel_heldout.hpp.  32 < K <= 1024: one wavefront per document, lane j on the topics j + 64 i; theta and the
+// Geometry: the walks of doc_model.hpp.  32 < K <= 1024: one wavefront per document, lane j on the topics j + 64 i; theta and the
 // credit stay in NI = 1 .. 16 registers per lane each and U sites are in flight.  K > 1024 (llda_attr_lds_kernel): both rows live
 // in LDS, 16 K bytes, one wavefront per workgroup; every lane reads and writes its own columns only, so no barrier is needed, and
 // a site's row is read twice (the second time from the caches).  K <= 32: a group of G = 8, 16 or 32 lanes per document; the groups
@@ -23,14 +23,9 @@ namespace {
 // rounds of "the best key after the one taken last" (r descending, then topic ascending), a wave-wide exchange each.
 // The whole row of phi_t is read even where theta is 0.  A document's outputs depend on its own inputs only.
 // ---------------------------------------------------------------------------------------------
-struct AttrParams {
-    const int64_t *doc_off;
-    const int32_t *word;
-    const int32_t *freq;
-    const double *theta;
-    const double *phi_t;
-    int64_t D, V, ld_theta, ld_phi, ld_out, ld_credit;
-    int32_t K, iters, top_m;
+struct AttrParams : DocModel {
+    int64_t ld_out, ld_credit;
+    int32_t iters, top_m;
     double alpha;
     double *theta_out;
     double *credit;
@@ -42,6 +37,7 @@ struct AttrParams {
 
 constexpr int ATTR_WAVES = 4;                           // wavefronts of a workgroup (wave and group kernels)
 constexpr int ATTR_MAX_TOP = 4;
+constexpr int attr_u(int NI) { return NI <= 2 ? 4 : NI <= 8 ? 2 : 1; }     // sites in flight in the wave kernel: NI = 1, 2 | 4, 8 | 16
 
 __device__ __forceinline__ bool attr_good(double p)
 {
@@ -116,105 +112,73 @@ __device__ __forceinline__ void attr_mstep(double (&th)[NI], const double (&cred
         num[i] = ((in >> i & 1u) && th[i] > 0.0) ? credit[i] + alpha : 0.0;
         part = (in >> i & 1u) ? part + num[i] : part;
     }
-    const double den = heldout_tree<G>(part);
+    const double den = doc_tree<G>(part);
     if (go && den > 0.0 && den < __longlong_as_double(0x7FF0000000000000ll)) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) th[i] = num[i] / den;
     }
 }
 
+// the document's counters and outputs
+__device__ __forceinline__ void attr_store(const AttrParams &P, int64_t d, int64_t tok, int64_t bad)
+{
+    if (P.tok) P.tok[d] = tok;
+    if (P.bad) P.bad[d] = bad;
+}
+
 template <int NI, int U, bool SITES>
 __global__ void __launch_bounds__(64 * ATTR_WAVES) llda_attr_wave_kernel(const AttrParams P)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int K = P.K;
-    int kc[NI];                                         // the lane's columns; column 0 where it has none
-    uint32_t in = 0;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int k = lane + 64 * i;
-        kc[i] = k < K ? k : 0;
-        if (k < K) in |= 1u << i;
-    }
+    const WaveCols<NI> C(lane, P.K);
     for (int64_t d = (int64_t)blockIdx.x * ATTR_WAVES + wave; d < P.D; d += (int64_t)gridDim.x * ATTR_WAVES) {
         const int64_t b = P.doc_off[d], e = P.doc_off[d + 1];
         const double *trow = P.theta + d * P.ld_theta;
         double th[NI], credit[NI];
 #pragma unroll
-        for (int i = 0; i < NI; ++i) th[i] = trow[kc[i]];
+        for (int i = 0; i < NI; ++i) th[i] = trow[C.kc[i]];
         int64_t tok = 0, bad = 0;
         for (int pass = 0;; ++pass) {
             const bool last = pass == P.iters || b == e;     // (a document without sites takes no step)
             tok = 0; bad = 0;
 #pragma unroll
             for (int i = 0; i < NI; ++i) credit[i] = 0.0;
-            for (int64_t s0 = b; s0 < e; s0 += 64) {
-                const int n = (int)(e - s0 < 64 ? e - s0 : 64);
-                const int32_t wv = lane < n ? P.word[s0 + lane] : -1;
-                const int32_t fv = lane < n ? (P.freq ? P.freq[s0 + lane] : 1) : 0;
-                for (int t = 0; t < n; t += U) {
-                    int32_t f[U];
-                    bool ok[U];
-                    double v[U][NI];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int tt = t + u < n ? t + u : n - 1;                    // (a repeat of the last site, not used)
-                        const int32_t w = __builtin_amdgcn_readlane(wv, tt);
-                        f[u] = __builtin_amdgcn_readlane(fv, tt);
-                        ok[u] = heldout_word_ok(w, P.V);
-                        const double *row = P.phi_t + (int64_t)(ok[u] ? w : 0) * P.ld_phi;
-#pragma unroll
-                        for (int i = 0; i < NI; ++i) v[u][i] = row[kc[i]];
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        if (t + u >= n) break;
-                        double part = 0.0;
-#pragma unroll
-                        for (int i = 0; i < NI; ++i) {
-                            v[u][i] = th[i] * v[u][i];                               // t_k
-                            part = (in >> i & 1u) ? part + v[u][i] : part;
-                        }
-                        const double p = heldout_tree<64>(part);
-                        const bool good = ok[u] && attr_good(p);
-                        tok += good ? f[u] : 0;
-                        bad += good ? 0 : f[u];
-                        if (!good) {
-                            if (SITES && last && lane == 0) attr_site_none(P, s0 + t + u);
-                            continue;
-                        }
-                        const double inv = 1.0 / p;
-                        const double g = (double)f[u] * inv;
-#pragma unroll
-                        for (int i = 0; i < NI; ++i) credit[i] = credit[i] + v[u][i] * g;
-                        if (SITES && last)
-                            attr_site_top<64>(P, s0 + t + u, lane == 0, [&](double pr, int pk, double &br, int &bk) {
-#pragma unroll
-                                for (int i = 0; i < NI; ++i)
-                                    if (in >> i & 1u) attr_offer(v[u][i] * inv, lane + 64 * i, pr, pk, br, bk);
-                            });
-                    }
+            wave_sites<NI, U>(P, C, th, lane, b, e, [&](int64_t s, int32_t f, bool ok, double p, const double (&t)[NI]) {
+                const bool good = ok && attr_good(p);
+                tok += good ? f : 0;
+                bad += good ? 0 : f;
+                if (!good) {
+                    if (SITES && last && lane == 0) attr_site_none(P, s);
+                    return;
                 }
-            }
+                const double inv = 1.0 / p;
+                const double g = (double)f * inv;
+#pragma unroll
+                for (int i = 0; i < NI; ++i) credit[i] = credit[i] + t[i] * g;
+                if (SITES && last)
+                    attr_site_top<64>(P, s, lane == 0, [&](double pr, int pk, double &br, int &bk) {
+#pragma unroll
+                        for (int i = 0; i < NI; ++i)
+                            if (C.in >> i & 1u) attr_offer(t[i] * inv, lane + 64 * i, pr, pk, br, bk);
+                    });
+            });
             if (last) break;
-            attr_mstep<NI, 64>(th, credit, in, P.alpha, true);
+            attr_mstep<NI, 64>(th, credit, C.in, P.alpha, true);
         }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            if (in >> i & 1u) {
-                if (P.theta_out) P.theta_out[d * P.ld_out + kc[i]] = th[i];
-                if (P.credit) P.credit[d * P.ld_credit + kc[i]] = credit[i];
+            if (C.in >> i & 1u) {
+                if (P.theta_out) P.theta_out[d * P.ld_out + C.kc[i]] = th[i];
+                if (P.credit) P.credit[d * P.ld_credit + C.kc[i]] = credit[i];
             }
         }
-        if (lane == 0) {
-            if (P.tok) P.tok[d] = tok;
-            if (P.bad) P.bad[d] = bad;
-        }
+        if (lane == 0) attr_store(P, d, tok, bad);
     }
 }
 
 // K > 1024: theta and the credit of the document in LDS (dynamic: 16 K bytes), one wavefront per workgroup.  Lane j touches the
-// entries j + 64 i of both rows and no other: nothing is shared between lanes, so there is no barrier.
+// entries j + 64 i of both rows and no other: nothing is shared between lanes, so there is no barrier.  A site's row is read twice
+// (the second time from the caches).
 template <bool SITES>
 __global__ void __launch_bounds__(64) llda_attr_lds_kernel(const AttrParams P)
 {
@@ -232,35 +196,23 @@ __global__ void __launch_bounds__(64) llda_attr_lds_kernel(const AttrParams P)
             const bool last = pass == P.iters || b == e;     // (a document without sites takes no step)
             tok = 0; bad = 0;
             for (int k = lane; k < K; k += 64) credit[k] = 0.0;
-            for (int64_t s0 = b; s0 < e; s0 += 64) {
-                const int n = (int)(e - s0 < 64 ? e - s0 : 64);
-                const int32_t wv = lane < n ? P.word[s0 + lane] : -1;
-                const int32_t fv = lane < n ? (P.freq ? P.freq[s0 + lane] : 1) : 0;
-                for (int t = 0; t < n; ++t) {
-                    const int32_t w = __builtin_amdgcn_readlane(wv, t), f = __builtin_amdgcn_readlane(fv, t);
-                    const bool ok = heldout_word_ok(w, P.V);
-                    const double *row = P.phi_t + (int64_t)(ok ? w : 0) * P.ld_phi;
-                    double part = 0.0;
-#pragma unroll 8
-                    for (int k = lane; k < K; k += 64) part = part + th[k] * row[k];
-                    const double p = heldout_tree<64>(part);
-                    const bool good = ok && attr_good(p);
-                    tok += good ? f : 0;
-                    bad += good ? 0 : f;
-                    if (!good) {
-                        if (SITES && last && lane == 0) attr_site_none(P, s0 + t);
-                        continue;
-                    }
-                    const double inv = 1.0 / p;
-                    const double g = (double)f * inv;
-#pragma unroll 8
-                    for (int k = lane; k < K; k += 64) credit[k] = credit[k] + (th[k] * row[k]) * g;
-                    if (SITES && last)
-                        attr_site_top<64>(P, s0 + t, lane == 0, [&](double pr, int pk, double &br, int &bk) {
-                            for (int k = lane; k < K; k += 64) attr_offer((th[k] * row[k]) * inv, k, pr, pk, br, bk);
-                        });
+            stream_sites(P, th, lane, b, e, [&](int64_t s, int32_t f, bool ok, double p, const double *row) {
+                const bool good = ok && attr_good(p);
+                tok += good ? f : 0;
+                bad += good ? 0 : f;
+                if (!good) {
+                    if (SITES && last && lane == 0) attr_site_none(P, s);
+                    return;
                 }
-            }
+                const double inv = 1.0 / p;
+                const double g = (double)f * inv;
+#pragma unroll 8
+                for (int k = lane; k < K; k += 64) credit[k] = credit[k] + (th[k] * row[k]) * g;
+                if (SITES && last)
+                    attr_site_top<64>(P, s, lane == 0, [&](double pr, int pk, double &br, int &bk) {
+                        for (int k = lane; k < K; k += 64) attr_offer((th[k] * row[k]) * inv, k, pr, pk, br, bk);
+                    });
+            });
             if (last) break;
             double part = 0.0;                          // the M-step; num takes the credit's place
             for (int k = lane; k < K; k += 64) {
@@ -268,7 +220,7 @@ __global__ void __launch_bounds__(64) llda_attr_lds_kernel(const AttrParams P)
                 credit[k] = num;
                 part = part + num;
             }
-            const double den = heldout_tree<64>(part);
+            const double den = doc_tree<64>(part);
             if (den > 0.0 && den < inf)
                 for (int k = lane; k < K; k += 64) th[k] = credit[k] / den;
         }
@@ -276,10 +228,7 @@ __global__ void __launch_bounds__(64) llda_attr_lds_kernel(const AttrParams P)
             if (P.theta_out) P.theta_out[d * P.ld_out + k] = th[k];
             if (P.credit) P.credit[d * P.ld_credit + k] = credit[k];
         }
-        if (lane == 0) {
-            if (P.tok) P.tok[d] = tok;
-            if (P.bad) P.bad[d] = bad;
-        }
+        if (lane == 0) attr_store(P, d, tok, bad);
     }
 }
 
@@ -287,68 +236,33 @@ __global__ void __launch_bounds__(64) llda_attr_lds_kernel(const AttrParams P)
 template <int G, bool SITES>
 __global__ void __launch_bounds__(64 * ATTR_WAVES) llda_attr_group_kernel(const AttrParams P, const int64_t n_tiles)
 {
-    constexpr int DPB = 64 * ATTR_WAVES / G;            // documents of a workgroup
-    constexpr int U = 4;
-    const int gl = threadIdx.x % G, dl = threadIdx.x / G;
-    const bool mine = gl < P.K;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t d = tile * DPB + dl;
-        const bool active = d < P.D;
-        const int64_t b = active ? P.doc_off[d] : 0, n = active ? P.doc_off[d + 1] - b : 0;
-        int64_t n_max = n;                              // the longest document of the wavefront
-#pragma unroll
-        for (int s = G; s < 64; s <<= 1) {
-            const int64_t o = __shfl_xor(n_max, s, 64);
-            n_max = o > n_max ? o : n_max;
-        }
-        double th[1] = {(active && mine) ? P.theta[d * P.ld_theta + gl] : 0.0}, credit[1] = {0.0};
+    group_docs<G, ATTR_WAVES>(P, n_tiles, [&](const GroupDoc &g) {
+        double th[1] = {g.th}, credit[1] = {0.0};
         int64_t tok = 0, bad = 0;
         for (int pass = 0;; ++pass) {
             const bool last = pass == P.iters;
             tok = 0; bad = 0;
             credit[0] = 0.0;
-            for (int64_t t = 0; t < n_max; t += U) {
-                int32_t f[U];
-                bool ok[U];
-                double v[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool live = t + u < n;
-                    const int32_t w = live ? P.word[b + t + u] : -1;
-                    f[u] = live ? (P.freq ? P.freq[b + t + u] : 1) : 0;
-                    ok[u] = heldout_word_ok(w, P.V);
-                    v[u] = (ok[u] && mine) ? P.phi_t[(int64_t)w * P.ld_phi + gl] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const double tk = th[0] * v[u];
-                    double part = 0.0;
-                    if (ok[u] && mine) part = part + tk;
-                    const double p = heldout_tree<G>(part);
-                    const bool live = t + u < n;
-                    const bool good = ok[u] && attr_good(p);
-                    tok += good ? f[u] : 0;                                          // (a site past the document's end: f = 0)
-                    bad += good ? 0 : f[u];
-                    const double inv = good ? 1.0 / p : 0.0;
-                    if (good && mine) credit[0] = credit[0] + tk * ((double)f[u] * inv);
-                    if (SITES && last)                                               // (a site that is not good offers nothing: all -1 / 0.0)
-                        attr_site_top<G>(P, b + t + u, live && gl == 0, [&](double pr, int pk, double &br, int &bk) {
-                            if (good && mine) attr_offer(tk * inv, gl, pr, pk, br, bk);
-                        });
-                }
-            }
+            group_sites<G>(P, g, th[0], [&](int64_t s, int32_t f, bool ok, bool live, double p, double tk) {
+                const bool good = ok && attr_good(p);
+                tok += good ? f : 0;                    // (a site past the document's end: f = 0)
+                bad += good ? 0 : f;
+                const double inv = good ? 1.0 / p : 0.0;
+                if (good && g.mine) credit[0] = credit[0] + tk * ((double)f * inv);
+                if (SITES && last)                      // (a site that is not good offers nothing: all -1 / 0.0)
+                    attr_site_top<G>(P, s, live && g.gl == 0, [&](double pr, int pk, double &br, int &bk) {
+                        if (good && g.mine) attr_offer(tk * inv, g.gl, pr, pk, br, bk);
+                    });
+            });
             if (last) break;
-            attr_mstep<1, G>(th, credit, mine ? 1u : 0u, P.alpha, n > 0);      // (a document without sites takes no step)
+            attr_mstep<1, G>(th, credit, g.mine ? 1u : 0u, P.alpha, g.n > 0);      // (a document without sites takes no step)
         }
-        if (active && mine) {
-            if (P.theta_out) P.theta_out[d * P.ld_out + gl] = th[0];
-            if (P.credit) P.credit[d * P.ld_credit + gl] = credit[0];
+        if (g.active && g.mine) {
+            if (P.theta_out) P.theta_out[g.d * P.ld_out + g.gl] = th[0];
+            if (P.credit) P.credit[g.d * P.ld_credit + g.gl] = credit[0];
         }
-        if (active && gl == 0) {
-            if (P.tok) P.tok[d] = tok;
-            if (P.bad) P.bad[d] = bad;
-        }
-    }
+        if (g.active && g.gl == 0) attr_store(P, g.d, tok, bad);
+    });
 }
 
 }  // namespace

@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(64 * WAVES) llda_leftright_kernel(const LrPara
                 const int zo = last ? (int)LR_NONE : __builtin_amdgcn_readfirstlane((int)s_z[m]);
                 if (!last && (uint32_t)zo == LR_NONE) continue;
                 const int w = __builtin_amdgcn_readfirstlane(s_word[m]);
-                const bool ok = heldout_word_ok(w, P.V);               // (m < n: the position was assigned, so it is)
+                const bool ok = word_ok(w, P.V);                       // (m < n: the position was assigned, so it is)
                 if (!last) lr_count<NI>(c, zo, lane, 1);
                 double x[NI];
                 weights(ok ? w : 0, x);
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(64 * WAVES) llda_leftright_kernel(const LrPara
                     double part = 0.0;
 #pragma unroll
                     for (int i = 0; i < NI; ++i) part = part + x[i];
-                    const double sum = heldout_tree<64>(part);
+                    const double sum = doc_tree<64>(part);
                     const double S = ok ? sum : nan;
                     pred = S / ((double)assigned + a_alpha);
                     draw = S > 0.0 && S < inf;
@@ -205,12 +205,7 @@ __global__ void __launch_bounds__(64 * WAVES) llda_leftright_kernel(const LrPara
                 const bool good = p > 0.0 && p < inf;
                 dtok += good ? 1 : 0;
                 dbad += good ? 0 : 1;
-                if (good) {                                             // frexp: exact, denormals included
-                    const double c2 = dm * __builtin_amdgcn_frexp_mant(p);
-                    const bool half = c2 < 0.5;
-                    dm = half ? c2 + c2 : c2;
-                    de += __builtin_amdgcn_frexp_exp(p) - (half ? 1 : 0);
-                }
+                if (good) pair_mul_frexp(dm, de, p);
             }
         }
         if (threadIdx.x == 0) {

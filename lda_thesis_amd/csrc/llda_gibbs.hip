@@ -42,6 +42,8 @@
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
 //   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
+//   doc_model.hpp       p(w | d) = theta[d] . phi_t[w] once: the 64-partial xor-tree sum, word_ok, the (mantissa, exponent) product and
+//                       the three walks over a document's sites -- wave_sites, stream_sites, group_docs / group_sites
 //   kernel_heldout.hpp  llda_heldout_wave_kernel, _wide_kernel, _group_kernel   per-document likelihood of held-out sites as (mantissa, exponent)
 //   kernel_attr.hpp     llda_attr_wave_kernel, _lds_kernel, _group_kernel           per-word label shares, credit and the EM fold-in
 //   kernel_leftright.hpp llda_leftright_kernel   left-to-right estimate of a document's likelihood: one particle per wavefront
@@ -79,6 +81,7 @@
 #include "kernel_wide.hpp"
 #include "kernel_topwords.hpp"
 #include "kernel_cooc.hpp"
+#include "doc_model.hpp"
 #include "kernel_heldout.hpp"
 #include "kernel_attr.hpp"
 #include "kernel_leftright.hpp"
@@ -361,35 +364,73 @@ void fill_schedule(const llda_layout &L, int32_t &last_leaf, int32_t &tail, int3
     }
 }
 
+// The document-model entry points (doc_model.hpp).  The geometry by K: a group of G lanes per document up to 32 topics, a wavefront
+// per document with NI registers per lane up to 1024, streaming beyond (NI = 0).  llda_left_to_right takes NI alone.
+struct DocGeom { int G, NI; };
+constexpr DocGeom doc_geom(int K)
+{
+    return {K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 0, K <= 64 ? 1 : K <= 128 ? 2 : K <= 256 ? 4 : K <= 512 ? 8 : K <= 1024 ? 16 : 0};
+}
+constexpr bool doc_geom_is(int K, int G, int NI) { return doc_geom(K).G == G && doc_geom(K).NI == NI; }
+static_assert(doc_geom_is(8, 8, 1) && doc_geom_is(9, 16, 1) && doc_geom_is(16, 16, 1) && doc_geom_is(17, 32, 1) && doc_geom_is(32, 32, 1), "group seams");
+static_assert(doc_geom_is(33, 0, 1) && doc_geom_is(64, 0, 1) && doc_geom_is(65, 0, 2) && doc_geom_is(128, 0, 2) && doc_geom_is(129, 0, 4) &&
+              doc_geom_is(256, 0, 4) && doc_geom_is(257, 0, 8) && doc_geom_is(512, 0, 8) && doc_geom_is(513, 0, 16) && doc_geom_is(1024, 0, 16) &&
+              doc_geom_is(1025, 0, 0), "wave seams");
+
+// what llda_heldout_loglik and llda_attribute check alike, in their order, and the fields they copy alike.  LLDA_OK with D = 0:
+// the caller has nothing to do; extra(): the checks of its own that come before that
+template <typename Args, typename Extra>
+int doc_model_args(const Args *a, DocModel &M, Extra &&extra)
+{
+    if (!a) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->ld_theta < a->K || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if (!extra()) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->theta || !a->phi_t) return LLDA_E_BAD_ARG;
+    if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->theta, a->phi_t, a->tok, a->bad) || misaligned(3, a->word, a->freq)) return LLDA_E_BAD_ARG;
+    M.doc_off = a->doc_off; M.word = a->word; M.freq = a->freq; M.theta = a->theta; M.phi_t = a->phi_t;
+    M.D = a->D; M.V = a->V; M.ld_theta = a->ld_theta; M.ld_phi = a->ld_phi; M.K = a->K;
+    return LLDA_OK;
+}
+
+inline dim3 doc_grid(int64_t blocks, int64_t cap = 1 << 20) { return dim3((unsigned)(blocks < cap ? blocks : cap)); }
+
+// the one ladder: group(G, grid, n_tiles), wave(NI, grid) or stream(grid) launches the family's kernel of that form
+template <int WAVES, typename FG, typename FW, typename FS>
+int launch_doc_model(const DocModel &M, FG &&group, FW &&wave, FS &&stream)
+{
+    const DocGeom g = doc_geom(M.K);
+    if (g.G) return visit_int<8, 16, 32>(g.G, [&](auto G) {
+        constexpr int docs = 64 * WAVES / G.value;
+        const int64_t n_tiles = (M.D + docs - 1) / docs;
+        group(G, doc_grid(n_tiles), n_tiles);
+        return launched();
+    });
+    const dim3 grid = doc_grid((M.D + WAVES - 1) / WAVES);
+    if (g.NI) return visit_int<1, 2, 4, 8, 16>(g.NI, [&](auto NI) {
+        wave(NI, grid);
+        return launched();
+    });
+    return stream(grid);
+}
+
 // llda_attribute: the kernel form by K (kernel_attr.hpp); SITES: the per-site outputs are wanted
 template <bool SITES>
 int launch_attr(const AttrParams &P, hipStream_t st)
 {
-    const int K = P.K;
     const dim3 block(64 * ATTR_WAVES);
-    if (K <= 32) {
-        const int G = K <= 8 ? 8 : K <= 16 ? 16 : 32, docs = 64 * ATTR_WAVES / G;
-        const int64_t n_tiles = (P.D + docs - 1) / docs;
-        const dim3 grid((unsigned)(n_tiles < (1 << 20) ? n_tiles : (1 << 20)));
-        if (G == 8) hipLaunchKernelGGL((llda_attr_group_kernel<8, SITES>), grid, block, 0, st, P, n_tiles);
-        else if (G == 16) hipLaunchKernelGGL((llda_attr_group_kernel<16, SITES>), grid, block, 0, st, P, n_tiles);
-        else hipLaunchKernelGGL((llda_attr_group_kernel<32, SITES>), grid, block, 0, st, P, n_tiles);
-    } else if (K <= 1024) {
-        const int64_t blocks = (P.D + ATTR_WAVES - 1) / ATTR_WAVES;
-        const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));
-        if (K <= 64) hipLaunchKernelGGL((llda_attr_wave_kernel<1, 4, SITES>), grid, block, 0, st, P);
-        else if (K <= 128) hipLaunchKernelGGL((llda_attr_wave_kernel<2, 4, SITES>), grid, block, 0, st, P);
-        else if (K <= 256) hipLaunchKernelGGL((llda_attr_wave_kernel<4, 2, SITES>), grid, block, 0, st, P);
-        else if (K <= 512) hipLaunchKernelGGL((llda_attr_wave_kernel<8, 2, SITES>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((llda_attr_wave_kernel<16, 1, SITES>), grid, block, 0, st, P);
-    } else {
-        const size_t lds = (size_t)2 * K * sizeof(double);                   // theta and credit: at most 123 008 bytes
-        const int rl = allow_lds(llda_attr_lds_kernel<SITES>, lds);
-        if (rl) return rl;
-        const dim3 grid((unsigned)(P.D < (1 << 16) ? P.D : (1 << 16)));
-        hipLaunchKernelGGL(llda_attr_lds_kernel<SITES>, grid, dim3(64), lds, st, P);
-    }
-    return launched();
+    return launch_doc_model<ATTR_WAVES>(P,
+        [&](auto G, dim3 grid, int64_t n_tiles) { hipLaunchKernelGGL((llda_attr_group_kernel<G.value, SITES>), grid, block, 0, st, P, n_tiles); },
+        [&](auto NI, dim3 grid) { hipLaunchKernelGGL((llda_attr_wave_kernel<NI.value, attr_u(NI.value), SITES>), grid, block, 0, st, P); },
+        [&](dim3) {
+            const size_t lds = (size_t)2 * P.K * sizeof(double);                 // theta and credit: at most 123 008 bytes
+            const int rl = allow_lds(llda_attr_lds_kernel<SITES>, lds);
+            if (rl) return rl;
+            hipLaunchKernelGGL(llda_attr_lds_kernel<SITES>, doc_grid(P.D, 1 << 16), dim3(64), lds, st, P);
+            return launched();
+        });
 }
 
 }  // namespace
@@ -923,59 +964,33 @@ int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64
 
 int llda_heldout_loglik(const llda_heldout_args *a, void *stream)
 {
-    if (!a) return LLDA_E_BAD_ARG;
-    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
-    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->ld_theta < a->K || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
-    if (a->D == 0) return LLDA_OK;
-    if (!a->doc_off || !a->word || !a->theta || !a->phi_t) return LLDA_E_BAD_ARG;
-    if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
-    if (misaligned(7, a->doc_off, a->theta, a->phi_t, a->mant, a->expo, a->tok, a->bad)) return LLDA_E_BAD_ARG;
-    if (misaligned(3, a->word, a->freq)) return LLDA_E_BAD_ARG;
     HeldoutParams P;
-    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.theta = a->theta; P.phi_t = a->phi_t;
-    P.D = a->D; P.V = a->V; P.ld_theta = a->ld_theta; P.ld_phi = a->ld_phi; P.K = a->K;
+    const int rc = doc_model_args(a, P, [] { return true; });
+    if (rc || a->D == 0) return rc;
+    if (misaligned(7, a->mant, a->expo)) return LLDA_E_BAD_ARG;
     P.mant = a->mant; P.expo = a->expo; P.tok = a->tok; P.bad = a->bad;
     hipStream_t st = (hipStream_t)stream;
     const dim3 block(64 * HELDOUT_WAVES);
-    const int K = a->K;
-    if (K <= 32) {
-        const int G = K <= 8 ? 8 : K <= 16 ? 16 : 32, docs = 64 * HELDOUT_WAVES / G;
-        const int64_t n_tiles = (a->D + docs - 1) / docs;
-        const dim3 grid((unsigned)(n_tiles < (1 << 20) ? n_tiles : (1 << 20)));
-        if (G == 8) hipLaunchKernelGGL(llda_heldout_group_kernel<8>, grid, block, 0, st, P, n_tiles);
-        else if (G == 16) hipLaunchKernelGGL(llda_heldout_group_kernel<16>, grid, block, 0, st, P, n_tiles);
-        else hipLaunchKernelGGL(llda_heldout_group_kernel<32>, grid, block, 0, st, P, n_tiles);
-    } else {
-        const int64_t blocks = (a->D + HELDOUT_WAVES - 1) / HELDOUT_WAVES;
-        const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));
-        if (K <= 64) hipLaunchKernelGGL((llda_heldout_wave_kernel<1, 4>), grid, block, 0, st, P);
-        else if (K <= 128) hipLaunchKernelGGL((llda_heldout_wave_kernel<2, 4>), grid, block, 0, st, P);
-        else if (K <= 256) hipLaunchKernelGGL((llda_heldout_wave_kernel<4, 4>), grid, block, 0, st, P);
-        else if (K <= 512) hipLaunchKernelGGL((llda_heldout_wave_kernel<8, 4>), grid, block, 0, st, P);
-        else if (K <= 1024) hipLaunchKernelGGL((llda_heldout_wave_kernel<16, 2>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL(llda_heldout_wide_kernel, grid, block, 0, st, P);
-    }
-    return launched();
+    return launch_doc_model<HELDOUT_WAVES>(P,
+        [&](auto G, dim3 grid, int64_t n_tiles) { hipLaunchKernelGGL(llda_heldout_group_kernel<G.value>, grid, block, 0, st, P, n_tiles); },
+        [&](auto NI, dim3 grid) { hipLaunchKernelGGL((llda_heldout_wave_kernel<NI.value, heldout_u(NI.value)>), grid, block, 0, st, P); },
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(llda_heldout_wide_kernel, grid, block, 0, st, P);
+            return launched();
+        });
 }
 
 int llda_attribute(const llda_attr_args *a, void *stream)
 {
-    if (!a) return LLDA_E_BAD_ARG;
-    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
-    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->ld_theta < a->K || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
-    if ((a->theta_out && a->ld_out < a->K) || (a->credit && a->ld_credit < a->K)) return LLDA_E_BAD_ARG;
-    if (a->iters < 0 || !(a->alpha >= 0.0) || a->top_m < 0 || a->top_m > LLDA_ATTR_MAX_TOP) return LLDA_E_BAD_ARG;
-    if (a->top_m > 0 && !a->site_idx != !a->site_val) return LLDA_E_BAD_ARG;
-    if (a->D == 0) return LLDA_OK;
-    if (!a->doc_off || !a->word || !a->theta || !a->phi_t) return LLDA_E_BAD_ARG;
-    if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
-    if ((a->theta_out && a->D > INT64_MAX / a->ld_out) || (a->credit && a->D > INT64_MAX / a->ld_credit)) return LLDA_E_BAD_ARG;
-    if (misaligned(7, a->doc_off, a->theta, a->phi_t, a->theta_out, a->credit, a->site_val, a->tok, a->bad)) return LLDA_E_BAD_ARG;
-    if (misaligned(3, a->word, a->freq, a->site_idx)) return LLDA_E_BAD_ARG;
     AttrParams P;
-    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.theta = a->theta; P.phi_t = a->phi_t;
-    P.D = a->D; P.V = a->V; P.ld_theta = a->ld_theta; P.ld_phi = a->ld_phi; P.ld_out = a->ld_out; P.ld_credit = a->ld_credit;
-    P.K = a->K; P.iters = a->iters; P.alpha = a->alpha;
+    const int rc = doc_model_args(a, P, [&] {
+        return !((a->theta_out && a->ld_out < a->K) || (a->credit && a->ld_credit < a->K) || a->iters < 0 || !(a->alpha >= 0.0) ||
+                 a->top_m < 0 || a->top_m > LLDA_ATTR_MAX_TOP || (a->top_m > 0 && !a->site_idx != !a->site_val));
+    });
+    if (rc || a->D == 0) return rc;
+    if ((a->theta_out && a->D > INT64_MAX / a->ld_out) || (a->credit && a->D > INT64_MAX / a->ld_credit)) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->theta_out, a->credit, a->site_val) || misaligned(3, a->site_idx)) return LLDA_E_BAD_ARG;
+    P.ld_out = a->ld_out; P.ld_credit = a->ld_credit; P.iters = a->iters; P.alpha = a->alpha;
     P.theta_out = a->theta_out; P.credit = a->credit; P.tok = a->tok; P.bad = a->bad;
     const bool sites = a->top_m > 0 && a->site_idx;                          // (top_m = 0 or no buffers: nothing in the site loop)
     P.top_m = sites ? a->top_m : 0; P.site_idx = sites ? a->site_idx : nullptr; P.site_val = sites ? a->site_val : nullptr;
@@ -1007,8 +1022,7 @@ int llda_left_to_right(const llda_leftright_args *a, void *stream)
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = lr_lds_bytes(P.R, P.cap);                            // at most 147 712 bytes
     const dim3 grid((unsigned)(P.D < (1 << 20) ? P.D : (1 << 20))), block(64 * P.R);
-    const int NI = P.K <= 64 ? 1 : P.K <= 128 ? 2 : P.K <= 256 ? 4 : P.K <= 512 ? 8 : 16;
-    return visit_int<1, 2, 4, 8, 16>(NI, [&](auto ni) {
+    return visit_int<1, 2, 4, 8, 16>(doc_geom(P.K).NI, [&](auto ni) {
         return visit_int<8, 16>(P.R <= 8 ? 8 : 16, [&](auto waves) {
             const auto kern = llda_leftright_kernel<ni.value, waves.value>;
             const int rl = allow_lds(kern, lds);

@@ -10,7 +10,7 @@ categorical draws over K topics; the kernel leaves the pair (mantissa, exponent)
 """
 import numpy as np
 
-from . import _native
+from . import _native, docmodel
 
 MAX_PARTICLES = _native.LR_MAX_PARTICLES
 MAX_TOKENS = _native.LR_MAX_TOKENS
@@ -69,43 +69,25 @@ def loglik(phi_t_dev, doc_off, word, alpha, particles, seed, stream_id=LR_STREAM
     import torch
     _native.lib()
     _native.require_device()
-    x = phi_t_dev
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 2):
-        raise ValueError("phi_t must be a two-dimensional float64 tensor on the device")
+    x = docmodel.matrix(phi_t_dev, "phi_t")
     dev = x.device
     V, K = int(x.shape[0]), int(x.shape[1])
-    if x.stride(1) != 1 or (V > 1 and x.stride(0) < K):
-        x = x.contiguous()
     if not 1 <= int(particles) <= MAX_PARTICLES:
         raise ValueError("particles must be in 1 .. %d" % MAX_PARTICLES)
 
-    def on_dev(a, dt):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=dev, dtype=dt).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt).contiguous()
-
-    off_h = doc_off.cpu().numpy() if isinstance(doc_off, torch.Tensor) else np.asarray(doc_off, dtype=np.int64)
-    D = int(off_h.shape[0]) - 1
-    if off_h.ndim != 1 or D < 0 or (D and (int(off_h[0]) < 0 or np.any(np.diff(off_h) < 0))):
-        raise ValueError("doc_off must hold D + 1 ascending offsets")
-    S = int(off_h[-1]) if D else 0
+    off_h, D, S = docmodel.check_offsets(doc_off)
     longest = int(np.diff(off_h).max()) if D else 0
     if longest > MAX_TOKENS:
         raise ValueError("a document holds %d tokens, more than %d" % (longest, MAX_TOKENS))
-    d_off, d_word = on_dev(off_h, torch.int64), on_dev(np.asarray(word, dtype=np.int64) if not isinstance(word, torch.Tensor) else word,
-                                                        torch.int32)
-    if int(d_word.numel()) == 0:
-        d_word = torch.zeros((1,), dtype=torch.int32, device=dev)      # (no token at all: the pointer must still be one)
-    if int(d_word.numel()) < S:
-        raise ValueError("word holds %d tokens, doc_off asks for %d" % (int(d_word.numel()), S))
+    d_off, d_word, _ = docmodel.stage(dev, off_h, word, None, S, unit="tokens")
     d_allowed = None
     if allowed is not None:
-        d_allowed = on_dev(allowed, torch.uint8)
+        d_allowed = docmodel.on_dev(allowed, torch.uint8, dev)
         if tuple(d_allowed.shape) != (D, K):
             raise ValueError("allowed must be (D, K) = (%d, %d)" % (D, K))
     d_ids = None
     if doc_ids is not None:
-        d_ids = on_dev(np.asarray(doc_ids, dtype=np.int64) if not isinstance(doc_ids, torch.Tensor) else doc_ids, torch.int64)
+        d_ids = docmodel.on_dev(doc_ids, torch.int64, dev)
         if int(d_ids.numel()) != D:
             raise ValueError("doc_ids must hold D = %d ids" % D)
     mant = torch.empty((D,), dtype=torch.float64, device=dev)

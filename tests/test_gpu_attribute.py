@@ -9,7 +9,7 @@ import attrref
 pytestmark = pytest.mark.gpu
 
 MAX_K = 7688
-KS = (1, 2, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 392, 512, 513, 1024, 1025, 1031, MAX_K)
+KS = (1, 2, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 256, 257, 392, 512, 513, 1024, 1025, 1031, MAX_K)
 GUARD = 8
 MAX_F = 2 ** 23 - 1
 PATTERN = {"float64": np.float64(-1234.5), "int64": np.int64(-0x123456789ABCDEF), "int32": np.int32(-0x1234567)}

@@ -10,7 +10,7 @@ import heldoutref
 pytestmark = pytest.mark.gpu
 
 MAX_K = 7688
-KS = (1, 2, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 392, 512, 513, 1031, MAX_K)
+KS = (1, 2, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 256, 257, 392, 512, 513, 1024, 1025, 1031, MAX_K)
 DS = (1, 3, 4, 5, 63, 64, 65, 257)
 GUARD = 8
 MAX_F = 2 ** 23 - 1
