@@ -576,6 +576,31 @@ int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t
 int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64_t V, int32_t K, int32_t n,
                    const int32_t *memb_off, const int32_t *memb, unsigned long long *co, void *stream);
 
+/* Sliding-window co-occurrence of listed words (additive to ABI 22): the integers of C_V, C_UCI and C_NPMI (Roeder, Both and
+ * Hinneburg, WSDM 2015), over documents given as token sequences in reading order.
+ *   tok_off [D+1] int64, tok [S] int32: the tokens of document d are tok[tok_off[d]] .. tok[tok_off[d+1]-1].  An id outside [0, V)
+ *            (-1) is a position without a dictionary word: it matches nothing and keeps its place in the window.  tok_off may point
+ *            into the middle of a longer array; a document holds fewer than 2^32 tokens.
+ *   memb_off, memb, co [K][n][n]: as in llda_word_cooc; a word's entries name every (topic, rank) at most once.
+ *   window   s, 0 <= s <= LLDA_WINDOW_MAX.  A document of L tokens has no window (L = 0), one window, the whole document (s = 0
+ *            or L <= s), or the L - s + 1 windows [w, w + s), w = 0 .. L - s.
+ *   For every window and topic k, with R = the ranks r for which some position of the window carries the word listed as (k, r):
+ *   co[k][i][j] += 1 for all i >= j in R.  co ACCUMULATES; entries with j > i are never written.  s = 0 gives what llda_word_cooc
+ *   gives on the same arrays; with s = 1 the diagonal is the token frequency of every listed word and the rest stays 0.
+ * One wavefront walks a document's windows and adds run lengths: a topic's pairs receive, in one add each, the number of
+ * consecutive windows over which its set R did not change.  Wavefront i takes the documents i, i + LLDA_WINDOW_MAX_WAVES, ... in a
+ * call of fewer than LLDA_WINDOW_AGG_MIN_DOCS documents, and every add is a 64-bit global atomic; a larger call adds to 64-bit LDS
+ * counters per slice of topics first and to co once per workgroup, when at most eight slices cover K.  Per-wavefront state is kept
+ * per slice of topics as well, so every K and n is taken.  All adds are integers: the result is independent of the form, the
+ * geometry and the order.
+ * D == 0 is a no-op.  LLDA_E_BAD_ARG: D < 0, V < 1, n outside 1 .. 16, window outside 0 .. LLDA_WINDOW_MAX, a NULL or misaligned
+ * pointer (D > 0); LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K; both before anything touches HIP. */
+#define LLDA_WINDOW_MAX 65535
+#define LLDA_WINDOW_MAX_WAVES 8192
+#define LLDA_WINDOW_AGG_MIN_DOCS 32768
+int llda_window_cooc(const int64_t *tok_off, const int32_t *tok, int64_t D, int64_t V, int32_t K, int32_t n, int32_t window,
+                     const int32_t *memb_off, const int32_t *memb, unsigned long long *co, void *stream);
+
 /* Per-document likelihood of held-out sites (additive to ABI 22): the scored half of document completion.
  *   doc_off [D+1] int64, word [S] int32, freq [S] int32 or NULL (= all 1; 0 <= f < 2^23): the sites to score, a CSR;
  *   theta [D][ld_theta] doubles, phi_t [V][ld_phi] doubles, word-major; both row-major in REFERENCE topic order (column = topic id,

@@ -347,6 +347,24 @@ class LabeledLDA(object):
             co, D = co.cpu().numpy(), len(doc_off) - 1
         return topics.coherence(co, D, measure, listed=idx.cpu().numpy())
 
+    def window_coherence(self, texts, n=10, measure="c_v", window=None):
+        """Sliding-window coherence of every label's n best words (float64 [K], NaN as in ``coherence``): measure = "c_v", "c_uci"
+        or "c_npmi" (Roeder, Both and Hinneburg 2015) over ``texts``, token lists in reading order -- for instance the ``docs`` the
+        constructor was given; a token outside the dictionary keeps its position and matches nothing.  window = None takes the
+        measure's usual width (``topics.DEFAULT_WINDOW``: 110 for c_v, 10 for the others).  The windows are counted on the device
+        (llda_window_cooc); the texts are counted whole on every rank: no collective."""
+        import torch
+        from . import topics
+        if measure not in topics.DEFAULT_WINDOW:
+            raise ValueError("measure must be 'c_v', 'c_uci' or 'c_npmi'")
+        window = topics.DEFAULT_WINDOW[measure] if window is None else window
+        sm = self._sampler
+        sm.check_status()
+        idx, _ = sm.top_words(n)
+        tok_off, tok = topics.token_csr(texts, self.dicti.token2id)
+        co = topics.window_cooccurrence(torch.from_numpy(tok_off).to(sm.device), torch.from_numpy(tok).to(sm.device), self.V, idx, window)
+        return topics.window_coherence(co.cpu().numpy(), topics.window_count(tok_off, window), measure, listed=idx.cpu().numpy())
+
     # ---- test time (reference LabeledLDA.py:155-212), on the device ----
     def prep4test(self, doc, seed=None, stream_id=None):
         """start state (ids, freqs, z_dn, n_dk) of one held-out token list: LabeledLDA.py:155-177."""

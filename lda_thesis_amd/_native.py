@@ -125,7 +125,7 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
 
            "llda_sweep", "llda_sweep_batch", "llda_commit_log", "llda_apply_rows", "llda_apply_delta", "llda_count_init", "llda_loglik", "llda_foldin",
            "llda_readout_phi", "llda_readout_theta", "llda_selftest_div", "llda_count_hist", "llda_rank_labels",
-           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_heldout_loglik", "llda_attribute",
+           "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_window_cooc", "llda_heldout_loglik", "llda_attribute",
            "llda_leftright_struct_bytes", "llda_left_to_right",
            "llda_nearest_struct_bytes", "llda_nearest_scratch_bytes", "llda_nearest_rows",
            "llda_label_struct_bytes", "llda_label_scratch_bytes", "llda_label_metrics", "llda_sets_struct_bytes", "llda_label_sets")
@@ -206,6 +206,8 @@ def lib():
     L.llda_top_words.argtypes = [_c_p, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i64, _c_p]
     L.llda_word_cooc.restype = ctypes.c_int
     L.llda_word_cooc.argtypes = [_c_p, _c_p, _c_i64, _c_i64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]
+    L.llda_window_cooc.restype = ctypes.c_int
+    L.llda_window_cooc.argtypes = [_c_p, _c_p, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]
     L.llda_heldout_loglik.restype = ctypes.c_int
     L.llda_heldout_loglik.argtypes = [ctypes.POINTER(LldaHeldoutArgs), _c_p]
     L.llda_attribute.restype = ctypes.c_int
@@ -455,6 +457,19 @@ def word_cooc(doc_off, word, D, V, K, n, memb_off, memb, co):
     the CSR doc_off (int64, at least D+1 entries) / word (int32)."""
     _launch(co, lib().llda_word_cooc, "llda_word_cooc", _ptr(doc_off), _ptr(word), int(D), int(V), int(K), int(n), _ptr(memb_off),
             _ptr(memb), _ptr(co))
+
+
+WINDOW_MAX = 65535   # LLDA_WINDOW_MAX: the widest sliding window of llda_window_cooc
+WINDOW_MAX_WAVES = 8192   # LLDA_WINDOW_MAX_WAVES: wavefront i of llda_window_cooc takes the documents i, i + 8192, ... in turn ...
+WINDOW_AGG_MIN_DOCS = 32768   # ... LLDA_WINDOW_AGG_MIN_DOCS: in calls of fewer documents; larger calls add to LDS counters first
+
+
+def window_cooc(tok_off, tok, D, V, K, n, window, memb_off, memb, co):
+    """llda_window_cooc on the current torch stream: co (int64 (K, n, n), accumulates) += in how many sliding windows of ``window``
+    tokens (0 = the whole document) the words of the membership table meet, over the D documents tok_off (int64, at least D+1
+    entries) / tok (int32 token ids in reading order; an id outside 0 .. V-1 holds its place and matches nothing)."""
+    _launch(co, lib().llda_window_cooc, "llda_window_cooc", _ptr(tok_off), _ptr(tok), int(D), int(V), int(K), int(n), int(window),
+            _ptr(memb_off), _ptr(memb), _ptr(co))
 
 
 HELDOUT_MAX_FREQ = 2 ** 23 - 1   # LLDA_HELDOUT_MAX_FREQ

@@ -42,6 +42,7 @@
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
 //   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
+//   kernel_window.hpp   llda_window_cooc_kernel   in how many sliding windows of the running text the listed words meet (C_V, C_UCI, C_NPMI)
 //   doc_model.hpp       p(w | d) = theta[d] . phi_t[w] once: the 64-partial xor-tree sum, word_ok, the (mantissa, exponent) product and
 //                       the three walks over a document's sites -- wave_sites, stream_sites, group_docs / group_sites
 //   kernel_heldout.hpp  llda_heldout_wave_kernel, _wide_kernel, _group_kernel   per-document likelihood of held-out sites as (mantissa, exponent)
@@ -81,6 +82,7 @@
 #include "kernel_wide.hpp"
 #include "kernel_topwords.hpp"
 #include "kernel_cooc.hpp"
+#include "kernel_window.hpp"
 #include "doc_model.hpp"
 #include "kernel_heldout.hpp"
 #include "kernel_attr.hpp"
@@ -959,6 +961,46 @@ int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64
     int64_t blocks = (D + COOC_WAVES - 1) / COOC_WAVES;
     if (blocks > LLDA_COOC_MAX_WAVES / COOC_WAVES) blocks = LLDA_COOC_MAX_WAVES / COOC_WAVES;
     hipLaunchKernelGGL(llda_word_cooc_kernel, dim3((unsigned)blocks), dim3(64 * COOC_WAVES), lds, st, P);
+    return launched();
+}
+
+int llda_window_cooc(const int64_t *tok_off, const int32_t *tok, int64_t D, int64_t V, int32_t K, int32_t n, int32_t window,
+                     const int32_t *memb_off, const int32_t *memb, unsigned long long *co, void *stream)
+{
+    if (D < 0 || V < 1 || V > INT32_MAX || n < 1 || n > 16 || window < 0 || window > LLDA_WINDOW_MAX) return LLDA_E_BAD_ARG;
+    if (K < 1 || K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (D == 0) return LLDA_OK;
+    if (!tok_off || !tok || !memb_off || !memb || !co) return LLDA_E_BAD_ARG;
+    if (misaligned(7, tok_off, co)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, tok, memb_off, memb)) return LLDA_E_BAD_ARG;
+    WindowParams P;
+    P.tok_off = tok_off; P.tok = tok; P.memb_off = memb_off; P.memb = memb; P.co = co;
+    P.D = D; P.V = V; P.K = K; P.n = n; P.window = window;
+    P.np = n * (n + 1) / 2; P.cw = (n + 1) / 2;
+    hipStream_t st = (hipStream_t)stream;
+    const int state = WINDOW_WAVES * (2 + P.cw) * (int)sizeof(uint32_t);       // bytes per topic: the wavefronts' masks, `since`, counts
+    // a large corpus: flushes go to counters per slice of topics in LDS, when few slices cover K (kernel_window.hpp)
+    const int agg = P.np * (int)sizeof(unsigned long long) + state;
+    const int agg_slices = (K + WINDOW_LDS_BYTES / agg - 1) / (WINDOW_LDS_BYTES / agg);
+    if (D >= LLDA_WINDOW_AGG_MIN_DOCS && agg_slices <= WINDOW_AGG_MAX_SLICES) {
+        P.ks = (K + agg_slices - 1) / agg_slices;
+        const size_t lds = (size_t)P.ks * agg;
+        const int rl = allow_lds(llda_window_cooc_kernel<true>, lds);
+        if (rl) return rl;
+        int64_t bx = (D + WINDOW_WAVES - 1) / WINDOW_WAVES;
+        const int64_t cap = WINDOW_AGG_BLOCKS / agg_slices > 1 ? WINDOW_AGG_BLOCKS / agg_slices : 1;
+        if (bx > cap) bx = cap;
+        hipLaunchKernelGGL(llda_window_cooc_kernel<true>, dim3((unsigned)bx, (unsigned)agg_slices), dim3(64 * WINDOW_WAVES), lds, st, P);
+        return launched();
+    }
+    const int slices = (K + WINDOW_LDS_BYTES / state - 1) / (WINDOW_LDS_BYTES / state);
+    P.ks = (K + slices - 1) / slices;
+    const size_t lds = (size_t)P.ks * state;
+    const int rl = allow_lds(llda_window_cooc_kernel<false>, lds);
+    if (rl) return rl;
+    int64_t blocks = (D + WINDOW_WAVES - 1) / WINDOW_WAVES;
+    if (blocks > LLDA_WINDOW_MAX_WAVES / WINDOW_WAVES) blocks = LLDA_WINDOW_MAX_WAVES / WINDOW_WAVES;
+    hipLaunchKernelGGL(llda_window_cooc_kernel<false>, dim3((unsigned)blocks, (unsigned)slices), dim3(64 * WINDOW_WAVES), lds, st, P);
     return launched();
 }
 

@@ -28,6 +28,9 @@ def build_parser():
     p.add_option("--coherence", dest="coherence", type="int", default=0, metavar="N",
                  help="after the report: UMass coherence of every label's N best words over the training corpus (llda_top_words, "
                       "llda_word_cooc), its mean and the five worst labels")
+    p.add_option("--window-coherence", dest="window_coherence", type="int", default=0, metavar="N",
+                 help="after the report: C_V coherence (sliding windows of 110 tokens) of every label's N best words over the training "
+                      "token lists (llda_top_words, llda_window_cooc), its mean and the five worst labels")
     p.add_option("--heldout-perplexity", action="store_true", dest="heldout_perplexity", default=False,
                  help="after the report: perplexity of the held-out documents by document completion (every second word of a "
                       "document folded in, the others scored on the GPU: llda_heldout_loglik)")
@@ -175,6 +178,19 @@ def report_coherence(model, n):
         print("  %-24s %10.3f  %s" % (names[k], coh[k], " ".join(model.v_to_w[int(v)] for v in idx[k] if v >= 0)))
 
 
+def report_window_coherence(model, texts, n):
+    """mean C_V coherence of the labels' n best words over the token lists ``texts`` and the five least coherent labels with those words"""
+    idx, _ = model.top_words(n)
+    coh = model.window_coherence(texts, n, "c_v")
+    names = list(model.labelmap.keys())
+    ok = np.flatnonzero(~np.isnan(coh))
+    print("-----------------------------------")
+    print("C_V coherence (top %d words), mean over %d of %d labels: " % (n, ok.shape[0], len(names)),
+          np.mean(coh[ok]) if ok.shape[0] else float("nan"))
+    for k in ok[np.argsort(coh[ok], kind="stable")[:5]]:
+        print("  %-24s %10.3f  %s" % (names[k], coh[k], " ".join(model.v_to_w[int(v)] for v in idx[k] if v >= 0)))
+
+
 def _header(lvl, it, corpus_file):
     print("Model:               Labeled LDA")
     print("Corpus:             ", "Abstracts" if corpus_file == "thesis_data3.csv" else "Full Texts")
@@ -225,6 +241,8 @@ def main(argv=None):
     (report_device if opt.device_metrics else report)(model, test, th, opt.lvl, opt.it, opt.file)
     if opt.coherence:
         report_coherence(model, opt.coherence)
+    if opt.window_coherence:
+        report_window_coherence(model, train[0], opt.window_coherence)
     if opt.heldout_perplexity:
         report_heldout(model, test, opt.it, opt.thinning)
     if opt.left_to_right:

@@ -1,4 +1,4 @@
-"""Top words per topic and topic coherence (``llda_top_words``, ``llda_word_cooc``, include/llda_gibbs.h).
+"""Top words per topic and topic coherence (``llda_top_words``, ``llda_word_cooc``, ``llda_window_cooc``, include/llda_gibbs.h).
 
 What a topic consists of, and whether its top words belong together.  The reference's ``topwords_per_topic``
 (LabeledLDA.py:241-254 there) sorts every row of the (K, V) float64 ``phi`` on the host; here one pass over the integer
@@ -12,6 +12,11 @@ descending, then word id ascending.  numpy's default ``argsort`` in the referenc
 
 Everything the device produces is an exact integer, independent of the geometry and of the number of ranks; ``umass`` and ``npmi``
 are numpy-only host functions of those integers.
+
+The sliding-window measures of Roeder, Both and Hinneburg ("Exploring the Space of Topic Coherence Measures", WSDM 2015) -- ``c_v``,
+``c_uci``, ``c_npmi`` -- count windows of the running text instead of documents: ``token_csr`` keeps the token order that a
+``doc2bow`` CSR drops, ``window_cooccurrence`` counts on the device (``llda_window_cooc``) and the three measures are host functions
+of its integers and of ``window_count``.
 """
 import numpy as np
 
@@ -121,6 +126,66 @@ def cooccurrence(doc_off, word, V, top_idx, out=None, table=None):
     return out
 
 
+def token_csr(texts, token2id):
+    """Token lists -> (tok_off int64 [D+1], tok int32 [S]), numpy: the ids of ``token2id`` in reading order; a token it does not
+    know becomes -1 and keeps its position."""
+    tok_off = np.zeros(len(texts) + 1, dtype=np.int64)
+    np.cumsum([len(t) for t in texts], out=tok_off[1:])
+    tok = np.fromiter((token2id.get(x, -1) for t in texts for x in t), dtype=np.int32, count=int(tok_off[-1]))
+    return tok_off, tok
+
+
+def _check_window(window):
+    window = int(window)
+    if not 0 <= window <= _native.WINDOW_MAX:
+        raise ValueError("window must be in 0 .. %d" % _native.WINDOW_MAX)
+    return window
+
+
+def window_count(tok_off, window):
+    """N, the number of windows ``window_cooccurrence`` visits: over the non-empty documents, L - window + 1 for a document of
+    L > window tokens and 1 for a shorter one; window = 0 (the whole document) gives the number of non-empty documents."""
+    s = _check_window(window)
+    off = tok_off.cpu().numpy() if hasattr(tok_off, "cpu") else np.asarray(tok_off)
+    L = np.diff(off.astype(np.int64))
+    L = L[L > 0]
+    return int(L.shape[0]) if s == 0 else int(np.maximum(1, L - s + 1).sum())
+
+
+def window_cooccurrence(tok_off, tok, V, top_idx, window, out=None, table=None):
+    """In how many sliding windows of ``window`` tokens the words listed in ``top_idx`` (K, n) meet, over the documents tok_off
+    (int64 [D+1]) / tok (int32 [S], token ids in reading order, -1 = no dictionary word), both device tensors: an int64 (K, n, n)
+    device tensor, co[k][i][j] for i >= j = the number of windows that hold both the word of rank i and the word of rank j of
+    topic k (the diagonal: the windows that hold the word); j > i stays as it was.  A document no longer than the window, or
+    window = 0, is one window.  ``out`` and ``table`` as in ``cooccurrence``."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    window = _check_window(window)
+    if not (isinstance(tok_off, torch.Tensor) and tok_off.is_cuda and tok_off.dtype == torch.int64 and tok_off.dim() == 1
+            and tok_off.numel() >= 1 and tok_off.is_contiguous()):
+        raise ValueError("tok_off must be a contiguous int64 [D+1] tensor on the device")
+    if not (isinstance(tok, torch.Tensor) and tok.dtype == torch.int32 and tok.dim() == 1 and tok.is_contiguous()
+            and tok.device == tok_off.device):
+        raise ValueError("tok must be a contiguous int32 [S] tensor on the device of tok_off")
+    dev = tok_off.device
+    t = _as_device_ids(top_idx, dev)
+    K, n = int(t.shape[0]), int(t.shape[1])
+    if out is None:
+        out = torch.zeros((K, n, n), dtype=torch.int64, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.int64 and tuple(out.shape) == (K, n, n) and out.is_contiguous()
+              and out.device == dev):
+        raise ValueError("out must be a contiguous int64 (K, n, n) tensor on the device of tok_off")
+    D = int(tok_off.numel()) - 1
+    if D == 0:
+        return out
+    memb_off, memb = table if table is not None else membership(t, V)
+    if memb.numel() == 0:
+        return out                                   # no topic lists a word: nothing to count
+    _native.window_cooc(tok_off, tok, D, int(V), K, n, window, memb_off, memb, out)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- host side, numpy only
 def _listed(co, listed):
     co = np.asarray(co)
@@ -190,3 +255,84 @@ def coherence(co, D, measure="umass", listed=None):
     if measure == "npmi":
         return npmi(co, D, listed=listed)
     raise ValueError("measure must be 'umass' or 'npmi'")
+
+
+# ---------------------------------------------------------------------------------------------- the sliding-window measures
+EPS = 1e-12                                          # gensim's constant
+DEFAULT_WINDOW = {"c_v": 110, "c_uci": 10, "c_npmi": 10}
+
+
+def _window_topics(co, listed):
+    """per topic: the symmetric float64 (m, m) table of the m listed ranks in rank order, c[a][b] = co[max][min] (the diagonal: c_a);
+    None for a topic that gets NaN -- fewer than two listed words, or a listed word no window holds"""
+    co, on = _listed(co, listed)
+    for k in range(co.shape[0]):
+        r = np.flatnonzero(on[k])
+        low = np.tril(co[k][np.ix_(r, r)])
+        if r.shape[0] < 2 or np.any(np.diagonal(low) == 0):
+            yield None
+            continue
+        yield (low + np.tril(low, -1).T).astype(np.float64)
+
+
+def _pmi_nlr(c, N):
+    """(pmi, nlr) of a symmetric float64 count table, element by element: p = c / N, p_aa = p_a"""
+    p = c / float(N)
+    pi = np.diagonal(p)
+    pmi = np.log((p + EPS) / (pi[:, None] * pi[None, :]))
+    return pmi, pmi / -np.log(p + EPS)
+
+
+def _pair_mean(co, N, listed, which):
+    out = []
+    for c in _window_topics(co, listed):
+        if c is None:
+            out.append(np.nan)
+            continue
+        term = np.ascontiguousarray(_pmi_nlr(c, N)[which][np.tril_indices(c.shape[0], -1)])
+        out.append(float(np.sum(term)) / term.shape[0])
+    return np.array(out, dtype=np.float64)
+
+
+def c_uci(co, N, listed=None):
+    """C_UCI per topic (float64 [K]) from ``window_cooccurrence``'s integers over N = ``window_count`` windows: the mean over the
+    pairs i > j of a topic's listed words of pmi(i, j) = log((p_ij + EPS) / (p_i p_j)), p = windows / N.  NaN as in ``umass``."""
+    return _pair_mean(co, N, listed, 0)
+
+
+def c_npmi(co, N, listed=None):
+    """C_NPMI per topic (float64 [K]): the mean over the same pairs of pmi(i, j) / -log(p_ij + EPS).  NaN as in ``umass``."""
+    return _pair_mean(co, N, listed, 1)
+
+
+def _cosine_mean(M):
+    """the mean over the rows u_a of a symmetric float64 (m, m) matrix of cos(u_a, v), v = the sum of the rows; a cosine with a zero
+    norm counts 0.0"""
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    m = M.shape[0]
+    v = np.array([np.sum(M[b]) for b in range(m)])                   # M is symmetric: the column sums, summed along rows
+    nv = np.sqrt(np.sum(v * v))
+    cos = np.zeros(m)
+    for a in range(m):
+        nu = np.sqrt(np.sum(M[a] * M[a]))
+        if nu != 0.0 and nv != 0.0:
+            cos[a] = np.sum(M[a] * v) / (nu * nv)
+    return float(np.sum(cos)) / m
+
+
+def c_v(co, N, listed=None):
+    """C_V per topic (float64 [K]): every listed word a gets the vector u_a = (nlr(a, b))_b over the listed words b (nlr = pmi /
+    -log(p_ab + EPS), p_aa = p_a), v is the sum of those vectors, and the value is the mean over a of the cosine of u_a and v
+    (0.0 where a norm is 0).  NaN as in ``umass``."""
+    return np.array([np.nan if c is None else _cosine_mean(_pmi_nlr(c, N)[1]) for c in _window_topics(co, listed)], dtype=np.float64)
+
+
+def window_coherence(co, N, measure="c_v", listed=None):
+    """``c_v``, ``c_uci`` or ``c_npmi`` by name."""
+    if measure == "c_v":
+        return c_v(co, N, listed=listed)
+    if measure == "c_uci":
+        return c_uci(co, N, listed=listed)
+    if measure == "c_npmi":
+        return c_npmi(co, N, listed=listed)
+    raise ValueError("measure must be 'c_v', 'c_uci' or 'c_npmi'")
