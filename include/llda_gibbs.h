@@ -890,6 +890,58 @@ typedef struct llda_sets_args {
 int llda_sets_struct_bytes(void);
 int llda_label_sets(const llda_sets_args *args, void *stream);
 
+/* The n best words of every topic by a float64 SCORE (additive to ABI 22): the distinctive words of a label --
+ * relevance (Sievert and Shirley 2014), lift -- and the ranking of a float64 matrix such as the running mean ph_hat.
+ *   score[w][k] = P_a(x[w][k]) / wdiv[w]
+ *   power    P_a(x) = x for a = 1, else ((x * x) * x) ...: a - 1 multiplications, left to right, each rounded, never contracted;
+ *            1 <= a <= 8.
+ *   divisor  wdiv [V] doubles or NULL (= every wdiv[w] is 1.0, nothing is divided).  The division is ONE IEEE division.
+ *            A word with wdiv[w] == 0 (either sign) is not ranked for any topic.
+ *   NaN      a NaN score is skipped and counted in n_nan[k].
+ *   order    score descending, compared as IEEE values (-0 == +0, +-inf ordinary), then word id ascending:
+ *            np.argsort(-score[cand, k], kind="stable") over the candidate words in id order.
+ *   x        two sources; exactly one of n_kw and mat is non-NULL:
+ *     counts   n_kw [V][KP] int32, word-major, device (group-layout) order, 16-byte aligned -- what llda_top_words takes.
+ *              x = ((double)c + beta) / den[k], the count converted as signed int32; den [KP] doubles in device order, or NULL:
+ *              den[k] = (double)n_k[k] + (double)V * beta with n_k [KP] int32 -- exactly llda_readout_phi, so x has the bits of
+ *              get_phi()[k][w].  Positions of the padding (pos_topic == -1) of n_kw, n_k and den influence nothing, whatever they
+ *              hold.  The conversion, the add and the division happen in the pass: it reads V*KP*4 bytes once, and wdiv.
+ *     matrix   mat [V][ld] doubles, ld >= K, columns in REFERENCE topic order, 8-byte aligned; x is the entry.
+ *   outputs  in REFERENCE topic order, each may be NULL on its own: top_idx [K][n] int32 word ids; top_score [K][n] doubles, the
+ *            bits as computed (a -0.0 stays one); n_nan [K] int32.  Entries beyond the number of ranked words of a topic are -1 and
+ *            the quiet NaN 0x7ff8000000000000.
+ * With lam = s / t the order of relevance lam * log(phi) + (1 - lam) * log(phi / p) within a topic is the order of
+ * phi^t / p^(t - s): a = t and wdiv = P_(t-s)(p); lam = 1 is phi itself (a = 1, no wdiv), lam = 0 is lift (a = 1, wdiv = p).
+ * Every output is a copy of an input, a count, or the result of the stated IEEE operations on one element: the result does not
+ * depend on chunking or geometry.  The key of a list entry is 96 bits, (score, word).  One bandwidth pass over the source in row
+ * chunks of LLDA_TOPW_CHUNK_ROWS words leaves partial lists in `scratch` (device memory, 8-byte aligned, at least
+ * llda_scored_words_scratch_bytes(V, K, n) bytes -- enough for either source --, contents irrelevant before and after); a second
+ * small launch merges them per topic.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG, before anything touches HIP: a NULL args; a struct_bytes other than
+ * sizeof(llda_scored_args); both of n_kw and mat, or neither; n outside 1 .. 16; a outside 1 .. 8; V < 1 or V > 2^31 - 1; ld < K
+ * or V x ld beyond an int64 (matrix); neither n_k nor den (counts); a NULL or too small scratch; a misaligned pointer (16 bytes:
+ * n_kw; 8: den, mat, wdiv, top_score, scratch; 4: n_k, top_idx, n_nan).
+ * llda_scored_struct_bytes and llda_scored_words_scratch_bytes are host only; the latter returns the same codes for a bad V, K, n. */
+typedef struct llda_scored_args {
+    uint32_t struct_bytes;       /* sizeof(llda_scored_args)                                     */
+    int32_t  K, n, a;
+    const int32_t *n_kw;         /* [dev] counts: [V][KP], else NULL                             */
+    const int32_t *n_k;          /* [dev] counts: [KP] or NULL (then den)                        */
+    const double  *den;          /* [dev] counts: [KP] or NULL (then n_k)                        */
+    const double  *mat;          /* [dev] matrix: [V][ld], else NULL                             */
+    const double  *wdiv;         /* [dev] [V] or NULL                                            */
+    int64_t  V, ld;              /* ld: matrix only                                              */
+    double   beta;               /* counts only                                                  */
+    int32_t *top_idx;            /* [dev] [K][n] or NULL                                         */
+    double  *top_score;          /* [dev] [K][n] or NULL                                         */
+    int32_t *n_nan;              /* [dev] [K] or NULL                                            */
+    void    *scratch;            /* [dev] work space                                             */
+    int64_t  scratch_bytes;
+} llda_scored_args;
+int llda_scored_struct_bytes(void);
+int64_t llda_scored_words_scratch_bytes(int64_t V, int32_t K, int32_t n);
+int llda_scored_words(const llda_scored_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

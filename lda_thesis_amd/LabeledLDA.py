@@ -303,12 +303,15 @@ class LabeledLDA(object):
         (reference LabeledLDA.py:256-265); evaluated by the llda_loglik HIP kernel."""
         return self._sampler.perplexity()
 
-    def topwords_per_topic(self, topwords=10, device=False):
+    def topwords_per_topic(self, topwords=10, device=False, lam=None):
         """[label, word, word, ...] for every label: reference LabeledLDA.py:241-254, from the downloaded ``get_phi()``.
         device=True takes the same lists from ``top_words`` (topwords <= 16): 8*K*topwords bytes come back instead of the (K, V)
         phi.  Ties then go by word id ascending, where the default ``argsort`` here and in the reference leaves the order of
-        equal phi open; without ties the two agree."""
+        equal phi open; without ties the two agree.  lam = a relevance in 0 .. 1: the DISTINCTIVE words of ``label_words`` instead."""
         names = list(self.labelmap.keys())
+        if lam is not None:
+            idx, _ = self.label_words(topwords, lam)
+            return [[names[k]] + [self.v_to_w[int(v)] for v in idx[k] if v >= 0] for k in range(self.K)]
         if device:
             idx, _ = self.top_words(topwords)
             return [[names[k]] + [self.v_to_w[int(v)] for v in idx[k] if v >= 0] for k in range(self.K)]
@@ -325,18 +328,47 @@ class LabeledLDA(object):
         idx, cnt = self._sampler.top_words(n)
         return idx.cpu().numpy(), cnt.cpu().numpy()
 
-    def coherence(self, n=10, measure="umass", docs=None):
+    def _label_words_device(self, n, lam, min_count, source="counts"):
+        """``label_words`` as device tensors (top_idx, top_score)"""
+        from . import topics
+        if source not in ("counts", "ph_hat"):
+            raise ValueError("source must be 'counts' or 'ph_hat'")
+        a, b = topics.relevance_powers(lam)
+        sm = self._sampler
+        sm.check_status()
+        # lam = 1 and no minimum count: nothing divides and no word is left out
+        wdiv = None if b == 0 and int(min_count) < 1 else topics.word_divisor(sm.word_totals().cpu().numpy(), b, min_count)
+        if source == "counts":
+            idx, score, _ = sm.scored_words(n, a, wdiv)
+        else:
+            idx, score, _ = topics.scored_words(self._phi_t_device(), self.K, n, a, wdiv)
+        return idx, score
+
+    def label_words(self, n=10, lam=0.6, min_count=1, source="counts"):
+        """The n <= 16 most DISTINCTIVE words of every label: ((K, n) int32 word ids, (K, n) float64 scores) as numpy arrays, padded
+        with -1 / NaN where a label ranks fewer than n words.  The order is that of LDAvis relevance (Sievert and Shirley 2014)
+        lam * log(phi) + (1 - lam) * log(phi / p), p = a word's share of the corpus, at lam rounded to a fraction s / t with t <= 8
+        (``topics.relevance_powers``): the score is phi^t / p^(t - s) -- no logarithm, so numpy restates it bit for bit -- descending,
+        then word id ascending (llda_scored_words).  lam = 1 ranks by phi, lam = 0 by lift phi / p.  Words that occur fewer than
+        max(min_count, 1) times in the corpus are not ranked (min_count < 1 at lam = 1: every word is).  source = "counts": phi of
+        the current counts; "ph_hat": the running mean of the thinning read-outs (the current phi before the first one).
+        n_k_v is replicated: no collective."""
+        idx, score = self._label_words_device(n, lam, min_count, source)
+        return idx.cpu().numpy(), score.cpu().numpy()
+
+    def coherence(self, n=10, measure="umass", docs=None, lam=None, min_count=1):
         """Topic coherence of every label's n best words (float64 [K]; NaN for a label with fewer than two words or with a top
         word that the corpus never holds): measure = "umass" (Mimno et al. 2011) or "npmi", over the training corpus or, with
         ``docs`` (token lists, through ``dicti.doc2bow``), over that reference corpus.  The document and co-document
         frequencies are counted on the device (llda_word_cooc).  Over the training corpus COLLECTIVE with several ranks;
-        ``docs`` are counted whole on every rank."""
+        ``docs`` are counted whole on every rank.  lam = a relevance in 0 .. 1: the coherence of the lists of
+        ``label_words(n, lam, min_count)`` instead of the most frequent words."""
         from . import topics
         if measure not in ("umass", "npmi"):
             raise ValueError("measure must be 'umass' or 'npmi'")
         sm = self._sampler
         sm.check_status()
-        idx, _ = sm.top_words(n)
+        idx = sm.top_words(n)[0] if lam is None else self._label_words_device(n, lam, min_count)[0]
         if docs is None:
             co, D = sm.word_cooccurrence(idx)
         else:
@@ -347,12 +379,13 @@ class LabeledLDA(object):
             co, D = co.cpu().numpy(), len(doc_off) - 1
         return topics.coherence(co, D, measure, listed=idx.cpu().numpy())
 
-    def window_coherence(self, texts, n=10, measure="c_v", window=None):
+    def window_coherence(self, texts, n=10, measure="c_v", window=None, lam=None, min_count=1):
         """Sliding-window coherence of every label's n best words (float64 [K], NaN as in ``coherence``): measure = "c_v", "c_uci"
         or "c_npmi" (Roeder, Both and Hinneburg 2015) over ``texts``, token lists in reading order -- for instance the ``docs`` the
         constructor was given; a token outside the dictionary keeps its position and matches nothing.  window = None takes the
         measure's usual width (``topics.DEFAULT_WINDOW``: 110 for c_v, 10 for the others).  The windows are counted on the device
-        (llda_window_cooc); the texts are counted whole on every rank: no collective."""
+        (llda_window_cooc); the texts are counted whole on every rank: no collective.  lam = a relevance in 0 .. 1: the coherence of
+        the lists of ``label_words(n, lam, min_count)`` instead of the most frequent words."""
         import torch
         from . import topics
         if measure not in topics.DEFAULT_WINDOW:
@@ -360,7 +393,7 @@ class LabeledLDA(object):
         window = topics.DEFAULT_WINDOW[measure] if window is None else window
         sm = self._sampler
         sm.check_status()
-        idx, _ = sm.top_words(n)
+        idx = sm.top_words(n)[0] if lam is None else self._label_words_device(n, lam, min_count)[0]
         tok_off, tok = topics.token_csr(texts, self.dicti.token2id)
         co = topics.window_cooccurrence(torch.from_numpy(tok_off).to(sm.device), torch.from_numpy(tok).to(sm.device), self.V, idx, window)
         return topics.window_coherence(co.cpu().numpy(), topics.window_count(tok_off, window), measure, listed=idx.cpu().numpy())

@@ -120,6 +120,13 @@ class LldaSetsArgs(ctypes.Structure):
                 ("tp", _c_p), ("fp", _c_p), ("fn", _c_p)]
 
 
+class LldaScoredArgs(ctypes.Structure):
+    """struct llda_scored_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("n", _c_i32), ("a", _c_i32), ("n_kw", _c_p), ("n_k", _c_p), ("den", _c_p),
+                ("mat", _c_p), ("wdiv", _c_p), ("V", _c_i64), ("ld", _c_i64), ("beta", _c_d), ("top_idx", _c_p), ("top_score", _c_p),
+                ("n_nan", _c_p), ("scratch", _c_p), ("scratch_bytes", _c_i64)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -128,7 +135,8 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_top_words_scratch_bytes", "llda_top_words", "llda_word_cooc", "llda_window_cooc", "llda_heldout_loglik", "llda_attribute",
            "llda_leftright_struct_bytes", "llda_left_to_right",
            "llda_nearest_struct_bytes", "llda_nearest_scratch_bytes", "llda_nearest_rows",
-           "llda_label_struct_bytes", "llda_label_scratch_bytes", "llda_label_metrics", "llda_sets_struct_bytes", "llda_label_sets")
+           "llda_label_struct_bytes", "llda_label_scratch_bytes", "llda_label_metrics", "llda_sets_struct_bytes", "llda_label_sets",
+           "llda_scored_struct_bytes", "llda_scored_words_scratch_bytes", "llda_scored_words")
 
 _LIB = None
 
@@ -232,6 +240,12 @@ def lib():
     L.llda_sets_struct_bytes.argtypes = []
     L.llda_label_sets.restype = ctypes.c_int
     L.llda_label_sets.argtypes = [ctypes.POINTER(LldaSetsArgs), _c_p]
+    L.llda_scored_struct_bytes.restype = ctypes.c_int
+    L.llda_scored_struct_bytes.argtypes = []
+    L.llda_scored_words_scratch_bytes.restype = _c_i64
+    L.llda_scored_words_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
+    L.llda_scored_words.restype = ctypes.c_int
+    L.llda_scored_words.argtypes = [ctypes.POINTER(LldaScoredArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -249,7 +263,8 @@ def lib():
     if L.llda_nearest_struct_bytes() != ctypes.sizeof(LldaNearestArgs):
         raise NativeError("LldaNearestArgs: binding has %d bytes, the library %d" % (ctypes.sizeof(LldaNearestArgs),
                                                                                      L.llda_nearest_struct_bytes()))
-    for name, struct, size in (("LldaLabelArgs", LldaLabelArgs, L.llda_label_struct_bytes()), ("LldaSetsArgs", LldaSetsArgs, L.llda_sets_struct_bytes())):
+    for name, struct, size in (("LldaLabelArgs", LldaLabelArgs, L.llda_label_struct_bytes()), ("LldaSetsArgs", LldaSetsArgs, L.llda_sets_struct_bytes()),
+                               ("LldaScoredArgs", LldaScoredArgs, L.llda_scored_struct_bytes())):
         if size != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
@@ -449,6 +464,29 @@ def top_words(n_kw, V, K, n, top_idx, top_cnt, scratch):
     top_words_scratch_bytes(V, K, n) bytes."""
     _launch(n_kw, lib().llda_top_words, "llda_top_words", _ptr(n_kw), int(V), int(K), int(n), _ptr(top_idx), _ptr(top_cnt),
             _ptr(scratch), int(scratch.numel() * scratch.element_size()))
+
+
+SCORED_MAX_A = 8        # llda_scored_args.a: the largest power
+
+
+def scored_words_scratch_bytes(V, K, n):
+    """llda_scored_words_scratch_bytes: bytes of work space llda_scored_words needs for either source (host only)."""
+    r = int(lib().llda_scored_words_scratch_bytes(int(V), int(K), int(n)))
+    if r < 0:
+        check(r, "llda_scored_words_scratch_bytes(V=%d, K=%d, n=%d)" % (V, K, n))
+    return r
+
+
+def scored_words(V, K, n, a, scratch, *, n_kw=None, n_k=None, den=None, beta=0.0, mat=None, ld=None, wdiv=None, top_idx=None,
+                 top_score=None, n_nan=None):
+    """llda_scored_words on the current torch stream: the n words of every topic with the best P_a(x) / wdiv.  x comes from n_kw
+    (int32 (V, KP), device order, with beta and n_k (int32 [KP]) or den (float64 [KP])) or from mat (float64 (V, ld), reference
+    topic order); wdiv float64 [V] or None; top_idx (K, n) int32, top_score (K, n) float64, n_nan (K,) int32 the outputs, each may be
+    None; scratch = a uint8 tensor of scored_words_scratch_bytes(V, K, n) bytes."""
+    args = LldaScoredArgs(ctypes.sizeof(LldaScoredArgs), int(K), int(n), int(a), _ptr(n_kw), _ptr(n_k), _ptr(den), _ptr(mat), _ptr(wdiv),
+                          int(V), int((0 if mat is None else mat.stride(0)) if ld is None else ld), float(beta), _ptr(top_idx),
+                          _ptr(top_score), _ptr(n_nan), _ptr(scratch), int(scratch.numel() * scratch.element_size()))
+    _launch(scratch, lib().llda_scored_words, "llda_scored_words", ctypes.byref(args))
 
 
 def word_cooc(doc_off, word, D, V, K, n, memb_off, memb, co):

@@ -41,6 +41,7 @@
 //   kernel_rank.hpp     llda_rank_labels_kernel   top-n labels and the harness metrics' ingredients from one sort per document
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
 //   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
+//   kernel_scored.hpp   llda_scored_words_kernel, llda_scored_merge_kernel   the n best words of every topic by a float64 score: 96-bit (score, word) keys
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
 //   kernel_window.hpp   llda_window_cooc_kernel   in how many sliding windows of the running text the listed words meet (C_V, C_UCI, C_NPMI)
 //   doc_model.hpp       p(w | d) = theta[d] . phi_t[w] once: the 64-partial xor-tree sum, word_ok, the (mantissa, exponent) product and
@@ -81,6 +82,7 @@
 #include "kernel_rank.hpp"
 #include "kernel_wide.hpp"
 #include "kernel_topwords.hpp"
+#include "kernel_scored.hpp"
 #include "kernel_cooc.hpp"
 #include "kernel_window.hpp"
 #include "doc_model.hpp"
@@ -1209,6 +1211,83 @@ int llda_label_sets(const llda_sets_args *a, void *stream)
     const int64_t rounds = (a->D + SETS_WAVES - 1) / SETS_WAVES;
     // every workgroup flushes K counters: a few workgroups per compute unit, each with many documents
     hipLaunchKernelGGL(llda_label_sets_kernel, dim3((unsigned)(rounds < 1024 ? rounds : 1024)), dim3(SETS_WAVES * 64), lds, (hipStream_t)stream, P);
+    return launched();
+}
+
+int llda_scored_struct_bytes(void) { return (int)sizeof(llda_scored_args); }
+
+// the geometry of llda_scored_words over `cols` columns (KP in counts mode, K in matrix mode) and the scratch it leaves behind
+struct ScoredGeometry { int32_t cpr, rpb, col_blocks; int64_t chunks; };
+
+static ScoredGeometry scored_geometry(int32_t cols, int64_t V)
+{
+    ScoredGeometry g;
+    g.cpr = (cols + 1) / 2;
+    g.rpb = 256 / g.cpr;
+    if (g.rpb < 1) g.rpb = 1;
+    if (g.rpb > SCORED_MAX_PHASES) g.rpb = SCORED_MAX_PHASES;
+    g.col_blocks = (g.cpr + 255) / 256;
+    g.chunks = (V + LLDA_TOPW_CHUNK_ROWS - 1) / LLDA_TOPW_CHUNK_ROWS;
+    return g;
+}
+
+// per (part, column): n scores, n word ids, one NaN count (2 * cpr columns: a multiple of 8 bytes)
+static int64_t scored_bytes(const ScoredGeometry &g, int32_t n) { return g.chunks * g.rpb * (2 * (int64_t)g.cpr) * (12 * n + 4); }
+
+int64_t llda_scored_words_scratch_bytes(int64_t V, int32_t K, int32_t n)
+{
+    if (V < 1 || V > INT32_MAX || n < 1 || n > 16) return LLDA_E_BAD_ARG;
+    int rc;
+    const llda_layout *Lp = layout_of(K, &rc);
+    if (rc) return rc;
+    const int64_t counts = scored_bytes(scored_geometry(Lp->KP, V), n), matrix = scored_bytes(scored_geometry(K, V), n);
+    return counts > matrix ? counts : matrix;
+}
+
+int llda_scored_words(const llda_scored_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_scored_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    const bool counts = a->n_kw != nullptr;
+    if (counts == (a->mat != nullptr)) return LLDA_E_BAD_ARG;
+    if (a->n < 1 || a->n > 16 || a->a < 1 || a->a > 8 || a->V < 1 || a->V > INT32_MAX) return LLDA_E_BAD_ARG;
+    if (counts ? (!a->n_k && !a->den) : (a->ld < a->K || a->ld > INT64_MAX / 8 / a->V)) return LLDA_E_BAD_ARG;
+    if (!a->scratch) return LLDA_E_BAD_ARG;
+    if (misaligned(15, a->n_kw) || misaligned(7, a->den, a->mat, a->wdiv, a->top_score) || misaligned(7, a->scratch)) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->n_k, a->top_idx, a->n_nan)) return LLDA_E_BAD_ARG;
+    int rc;
+    const llda_layout *Lp = layout_of(a->K, &rc);
+    if (rc) return rc;
+    const llda_layout &L = *Lp;
+    const ScoredGeometry g = scored_geometry(counts ? L.KP : a->K, a->V);
+    if (a->scratch_bytes < scored_bytes(g, a->n)) return LLDA_E_BAD_ARG;
+    ScoredParams P;
+    memset(&P, 0, sizeof P);
+    P.n_kw = reinterpret_cast<const int2 *>(a->n_kw);
+    P.n_k = a->n_k; P.den = a->den; P.mat = a->mat; P.wdiv = a->wdiv;
+    P.V = a->V; P.ld = a->ld; P.beta = a->beta; P.vbeta = (double)a->V * a->beta;
+    P.cpr = g.cpr; P.rpb = g.rpb; P.n = a->n; P.a = a->a; P.C = 2 * g.cpr; P.K = a->K; P.G = L.G; P.T = L.T;
+    P.parts = g.chunks * g.rpb;
+    const int64_t lists = P.parts * P.C * a->n;
+    P.part_score = static_cast<double *>(a->scratch);
+    P.part_id = reinterpret_cast<uint32_t *>(P.part_score + lists);
+    P.part_nan = reinterpret_cast<int32_t *>(P.part_id + lists);
+    P.top_idx = a->top_idx; P.top_score = a->top_score; P.n_nan = a->n_nan;
+    for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { P.leaf_start[p] = L.leaf_start[p]; P.leaf_len[p] = L.leaf_len[p]; }
+    const dim3 grid((unsigned)g.chunks, (unsigned)g.col_blocks), merge_grid((unsigned)(counts ? L.KP : a->K));
+    hipStream_t st = (hipStream_t)stream;
+    // 16-byte loads of a matrix row pair need the base 16-byte aligned and an even leading dimension
+    const int mode = counts ? SCORED_COUNTS : (!misaligned(15, a->mat) && !(a->ld & 1)) ? SCORED_MATRIX_VEC : SCORED_MATRIX;
+#define LLDA_SCORED_MODE(N_, M_) hipLaunchKernelGGL((llda_scored_words_kernel<N_, M_>), grid, dim3(256), 0, st, P)
+#define LLDA_SCORED(N_) { if (mode == SCORED_COUNTS) LLDA_SCORED_MODE(N_, SCORED_COUNTS); \
+                          else if (mode == SCORED_MATRIX_VEC) LLDA_SCORED_MODE(N_, SCORED_MATRIX_VEC); \
+                          else LLDA_SCORED_MODE(N_, SCORED_MATRIX); \
+                          hipLaunchKernelGGL(llda_scored_merge_kernel<N_>, merge_grid, dim3(64), 0, st, P); }
+    if (a->n <= 4) LLDA_SCORED(4)
+    else if (a->n <= 10) LLDA_SCORED(10)
+    else LLDA_SCORED(16)
+#undef LLDA_SCORED
+#undef LLDA_SCORED_MODE
     return launched();
 }
 

@@ -31,6 +31,12 @@ def build_parser():
     p.add_option("--window-coherence", dest="window_coherence", type="int", default=0, metavar="N",
                  help="after the report: C_V coherence (sliding windows of 110 tokens) of every label's N best words over the training "
                       "token lists (llda_top_words, llda_window_cooc), its mean and the five worst labels")
+    p.add_option("--label-words", dest="label_words", type="int", default=0, metavar="N",
+                 help="after the report: every label's N most distinctive words (relevance --relevance; llda_scored_words) next to its "
+                      "N most frequent ones; with --coherence / --window-coherence also the mean coherence of both lists")
+    p.add_option("--relevance", dest="relevance", type="float", default=0.6, metavar="L",
+                 help="the weight of --label-words between a word's probability under the label (1) and its lift over the corpus (0), "
+                      "as in LDAvis; rounded to a fraction with a denominator of at most 8")
     p.add_option("--heldout-perplexity", action="store_true", dest="heldout_perplexity", default=False,
                  help="after the report: perplexity of the held-out documents by document completion (every second word of a "
                       "document folded in, the others scored on the GPU: llda_heldout_loglik)")
@@ -191,6 +197,26 @@ def report_window_coherence(model, texts, n):
         print("  %-24s %10.3f  %s" % (names[k], coh[k], " ".join(model.v_to_w[int(v)] for v in idx[k] if v >= 0)))
 
 
+def report_label_words(model, n, lam, coherence_n=0, window_n=0, texts=None):
+    """every label's n most distinctive words (LabeledLDA.label_words) next to its n most frequent ones; coherence_n / window_n > 0: the
+    mean UMass / C_V coherence of both kinds of list"""
+    frequent, _ = model.top_words(n)
+    distinctive, _ = model.label_words(n, lam)
+    names = list(model.labelmap.keys())
+    words = lambda row: " ".join(model.v_to_w[int(v)] for v in row if v >= 0)
+    print("-----------------------------------")
+    print("Label words (top %d): most frequent | most distinctive (relevance %g):" % (n, lam))
+    for k, name in enumerate(names):
+        print("  %-24s %s | %s" % (name, words(frequent[k]), words(distinctive[k])))
+    mean = lambda coh: np.mean(coh[~np.isnan(coh)]) if (~np.isnan(coh)).any() else float("nan")
+    if coherence_n:
+        print("UMass coherence (top %d words), mean: frequent %s, distinctive %s"
+              % (coherence_n, mean(model.coherence(coherence_n, "umass")), mean(model.coherence(coherence_n, "umass", lam=lam))))
+    if window_n:
+        print("C_V coherence (top %d words), mean: frequent %s, distinctive %s"
+              % (window_n, mean(model.window_coherence(texts, window_n, "c_v")), mean(model.window_coherence(texts, window_n, "c_v", lam=lam))))
+
+
 def _header(lvl, it, corpus_file):
     print("Model:               Labeled LDA")
     print("Corpus:             ", "Abstracts" if corpus_file == "thesis_data3.csv" else "Full Texts")
@@ -243,6 +269,8 @@ def main(argv=None):
         report_coherence(model, opt.coherence)
     if opt.window_coherence:
         report_window_coherence(model, train[0], opt.window_coherence)
+    if opt.label_words:
+        report_label_words(model, opt.label_words, opt.relevance, opt.coherence, opt.window_coherence, train[0])
     if opt.heldout_perplexity:
         report_heldout(model, test, opt.it, opt.thinning)
     if opt.left_to_right:

@@ -929,6 +929,17 @@ class GibbsSampler(object):
         from . import topics
         return topics.top_words(self.n_kw, self.K, n)
 
+    def word_totals(self):
+        """n_w, how often every word occurs in the corpus: an int64 [V] device tensor, the sum of n_kw over the K positions that hold a
+        topic (never the padding).  n_kw is replicated on every rank: one torch reduction, no collective."""
+        return self.n_kw[:, self._topic_pos].sum(dim=1, dtype=torch.int64)
+
+    def scored_words(self, n, a=1, wdiv=None):
+        """the n best words of every topic by P_a(phi) / wdiv (``topics.scored_words`` on this sampler's n_kw, n_k and beta): device
+        tensors (top_idx (K, n) int32, top_score (K, n) float64, n_nan (K,) int32) in reference topic order.  No collective."""
+        from . import topics
+        return topics.scored_words(self.n_kw, self.K, n, a, wdiv, n_k=self.n_k, beta=self.beta)
+
     def word_cooccurrence(self, top_idx):
         """document and co-document frequencies of the words of ``top_idx`` (K, n) over this sampler's documents (``topics.cooccurrence``):
         (co, D_total), co an int64 (K, n, n) numpy array.  COLLECTIVE with several ranks: ONE int64 SUM all-reduce of the K*n*n counts

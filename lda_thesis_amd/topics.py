@@ -17,6 +17,11 @@ The sliding-window measures of Roeder, Both and Hinneburg ("Exploring the Space 
 ``c_uci``, ``c_npmi`` -- count windows of the running text instead of documents: ``token_csr`` keeps the token order that a
 ``doc2bow`` CSR drops, ``window_cooccurrence`` counts on the device (``llda_window_cooc``) and the three measures are host functions
 of its integers and of ``window_count``.
+
+Which words set a label apart is a float score, not a count: ``scored_words`` (``llda_scored_words``) ranks P_a(x) / wdiv with
+96-bit (score, word) keys, ``relevance_powers`` turns LDAvis's lam (Sievert and Shirley 2014) into the integer powers whose
+quotient has the order of relevance without a logarithm, and ``word_divisor`` builds the divisor from the words' totals.  Every
+score is a fixed sequence of IEEE multiplications and one division of one element: numpy restates it bit for bit.
 """
 import numpy as np
 
@@ -55,6 +60,95 @@ def top_words(n_kw, K, n, stream=None):
         _native.top_words(n_kw, V, K, n, top_idx, top_cnt, scratch)
         n_kw.record_stream(stream)
     return top_idx, top_cnt
+
+
+def relevance_powers(lam):
+    """(a, b) such that, within a topic, the order of LDAvis relevance lam * log(phi) + (1 - lam) * log(phi / p) is the order of
+    phi^a / p^b: with lam = s / t (``Fraction(lam).limit_denominator(8)``) a = t and b = t - s.  1 -> (1, 0): phi itself; 0 -> (1, 1):
+    lift; 0.5 -> (2, 1); 0.6 -> (5, 2)."""
+    from fractions import Fraction
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lam must be in 0 .. 1")
+    f = Fraction(lam).limit_denominator(_native.SCORED_MAX_A)
+    return f.denominator, f.denominator - f.numerator
+
+
+def _power(x, a):
+    """P_a(x): a - 1 multiplications, left to right, each rounded"""
+    p = x
+    for _ in range(int(a) - 1):
+        p = p * x
+    return p
+
+
+def word_divisor(n_w, b, min_count=1):
+    """The divisor of ``scored_words`` for the power b of a word's overall share (numpy float64 [V]): p = n_w / sum(n_w),
+    wdiv = P_b(p) by b - 1 multiplications (ones for b = 0), and 0 -- the word is not ranked -- where n_w < max(min_count, 1)."""
+    n_w = np.asarray(n_w)
+    b = int(b)
+    if not 0 <= b <= _native.SCORED_MAX_A:
+        raise ValueError("b must be in 0 .. %d" % _native.SCORED_MAX_A)
+    p = n_w.astype(np.float64) / float(n_w.sum())
+    wdiv = np.ones(p.shape, dtype=np.float64) if b == 0 else _power(p, b)
+    wdiv[n_w < max(int(min_count), 1)] = 0.0
+    return wdiv
+
+
+def scored_words(source, K, n, a=1, wdiv=None, *, n_k=None, beta=None, den=None, stream=None):
+    """The n best words of every topic by score = P_a(x) / wdiv (``llda_scored_words``): device tensors (top_idx (K, n) int32,
+    top_score (K, n) float64, n_nan (K,) int32) in reference topic order, padded with -1 / NaN where a topic ranks fewer than n
+    words.  ``source`` is either ``n_kw`` -- int32 (V, KP) on the device, word-major, device order; x is then phi of the counts,
+    with ``beta`` and ``n_k`` (int32 [KP]) or ``den`` (float64 [KP]) as ``llda_readout_phi`` takes them -- or a float64 (V, ld)
+    matrix on the device with its columns in reference topic order (x is the entry).  wdiv: float64 [V] (numpy or tensor) or
+    None; a word whose wdiv is 0 is not ranked.  Enqueues on ``stream`` (default: the current one)."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    n, K, a = _check_n(n), int(K), int(a)
+    if not 1 <= a <= _native.SCORED_MAX_A:
+        raise ValueError("a must be in 1 .. %d" % _native.SCORED_MAX_A)
+    if not (isinstance(source, torch.Tensor) and source.is_cuda and source.dim() == 2 and source.dtype in (torch.int32, torch.float64)):
+        raise ValueError("source must be an int32 (V, KP) or a float64 (V, ld) tensor on the device")
+    counts = source.dtype == torch.int32
+    dev = source.device
+    V = int(source.shape[0])
+    if counts:
+        if beta is None or (n_k is None) == (den is None):
+            raise ValueError("counts need beta and exactly one of n_k and den")
+        source = source.contiguous()
+        for name, t, dt in (("n_k", n_k, torch.int32), ("den", den, torch.float64)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.dim() == 1
+                                      and t.is_contiguous() and int(t.numel()) == int(source.shape[1])):
+                raise ValueError("%s must be a contiguous %s [KP] tensor on the device of the counts" % (name, dt))
+    else:
+        if n_k is not None or den is not None or beta is not None:
+            raise ValueError("n_k, den and beta belong to the counts")
+        if int(source.shape[1]) < K:
+            raise ValueError("a matrix needs at least K columns")
+        if source.stride(1) != 1 or source.stride(0) < int(source.shape[1]):
+            source = source.contiguous()
+    if wdiv is not None:
+        wdiv = torch.as_tensor(wdiv).to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(wdiv.shape) != (V,):
+            raise ValueError("wdiv must hold one value per word")
+    nbytes = _native.scored_words_scratch_bytes(V, K, n)
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(stream):
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        top_idx = torch.empty((K, n), dtype=torch.int32, device=dev)
+        top_score = torch.empty((K, n), dtype=torch.float64, device=dev)
+        n_nan = torch.empty((K,), dtype=torch.int32, device=dev)
+        if counts:
+            _native.scored_words(V, K, n, a, scratch, n_kw=source, n_k=n_k, den=den, beta=float(beta), wdiv=wdiv, top_idx=top_idx,
+                                 top_score=top_score, n_nan=n_nan)
+        else:
+            _native.scored_words(V, K, n, a, scratch, mat=source, wdiv=wdiv, top_idx=top_idx, top_score=top_score, n_nan=n_nan)
+        for t in (source, n_k, den, wdiv):
+            if t is not None:
+                t.record_stream(stream)
+    return top_idx, top_score, n_nan
 
 
 def _as_device_ids(top_idx, device=None):
