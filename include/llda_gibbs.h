@@ -942,6 +942,96 @@ int llda_scored_struct_bytes(void);
 int64_t llda_scored_words_scratch_bytes(int64_t V, int32_t K, int32_t n);
 int llda_scored_words(const llda_scored_args *args, void *stream);
 
+/* ECDF ranks of every word within every topic (additive to ABI 22): the integers FREX (Bischof and Airoldi 2012)
+ * and topic exclusivity are made of.  llda_scored_words ranks one float score; a rank-based score needs every topic's whole
+ * empirical distribution over the vocabulary: a sort of V keys per topic, done by the engine of llda_label_metrics.
+ *   mat [V][ld] doubles, word-major, columns in REFERENCE topic order, ld >= K; columns >= K are never read.
+ *   tot[w]   sum64(mat[w][0 .. K-1]) -- the fixed-order sum of llda_heldout_loglik (64 partials from +0.0, then the xor tree) -- over
+ *            ALL K columns, whatever the ranked range.
+ *   cand [V] uint8 or NULL (= every word).  A word is a CANDIDATE iff cand[w] != 0 and 0 < tot[w] < inf, in both modes: the same set
+ *            for every column, and every entry of a candidate's row is finite.  Vc, the number of candidates, goes to n_cand[0].
+ *   value    mode 0: v[w][k] = mat[w][k];  mode 1: v[w][k] = mat[w][k] / tot[w], ONE IEEE division: the exclusivity.
+ *   rank     [n_labels][V] int32, row l for column first + l <= K - 1 (no other column is ranked: a caller short of scratch walks the
+ *            columns in batches and gets the same bits).  For a candidate #{candidates u : v[u][k] <= v[w][k]}, compared as IEEE
+ *            values (-0 == +0): the column's ECDF times Vc, np.searchsorted(np.sort(v[cand, k]), v[w, k], side="right"), in 1 .. Vc;
+ *            equal values share the rank of the group's last member.  For any other word 0.
+ *   value    [n_labels][V] doubles or NULL: the bits of v (a -0.0 stays one); any other word gets the quiet NaN 0x7ff8000000000000.
+ * 1 <= V <= 2^30 (the payload word << 1 keeps 32 bits); n_labels == 0 is a no-op that writes nothing, not even n_cand.
+ * Every output is an integer or the result of one stated IEEE operation on one element: bit-identical whatever the chunk, the batches
+ * or the geometry.
+ *   chunk    as in llda_label_args: 0, or 256 for tests.
+ *   scratch  at least llda_ecdf_scratch_bytes(V, n_labels, chunk) bytes = 2 x 12 x Vp x n_labels + 8 x V + 16, Vp = V rounded up to
+ *            the chunk; contents irrelevant before and after.
+ * Alignment: mat, value, n_cand and scratch 8-byte aligned, rank 4-byte aligned.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG, before anything touches HIP: a NULL args; a struct_bytes other than
+ * sizeof(llda_ecdf_args); first < 0, n_labels < 0 or first + n_labels > K; ld < K; V < 1 or V > 2^30; a chunk other than 0 and 256; a
+ * mode other than 0 and 1; and with n_labels > 0: a NULL mat, rank or scratch, V x ld beyond an int64, a misaligned pointer,
+ * scratch_bytes too small.
+ * llda_ecdf_scratch_bytes and llda_ecdf_struct_bytes are host only; the former returns LLDA_E_BAD_ARG for the same bad sizes. */
+#define LLDA_ECDF_MAX_V (1 << 30)
+typedef struct llda_ecdf_args {
+    uint32_t struct_bytes;       /* sizeof(llda_ecdf_args)                                       */
+    int32_t  K, first, n_labels;
+    int32_t  chunk, mode;
+    const double  *mat;          /* [dev] [V][ld]                                                */
+    const uint8_t *cand;         /* [dev] [V] or NULL                                            */
+    int64_t  V, ld;
+    int32_t  *rank;              /* [dev] [n_labels][V]                                          */
+    double   *value;             /* [dev] [n_labels][V] or NULL                                  */
+    int64_t  *n_cand;            /* [dev] [1] or NULL                                            */
+    void     *scratch;           /* [dev]                                                        */
+    int64_t  scratch_bytes;
+} llda_ecdf_args;
+int llda_ecdf_struct_bytes(void);
+int64_t llda_ecdf_scratch_bytes(int64_t V, int32_t n_labels, int32_t chunk);
+int llda_ecdf_ranks(const llda_ecdf_args *args, void *stream);
+
+/* The n best words of every topic by TWO ranks (additive to ABI 22): FREX, the harmonic mean of a word's frequency
+ * rank and its exclusivity rank within the topic,  FREX = 1 / (omega / F_e + (1 - omega) / F_f),  F = rank / Vc,  omega = s / t.
+ *   rank_f, rank_e [n_labels][V] int32: what llda_ecdf_ranks wrote in mode 0 and mode 1 -- or any numbers in 0 .. Vc.  A word is
+ *            RANKED in column l iff both of its ranks are in 1 .. Vc (anything else counts as 0: not ranked).
+ *   cost     c = s / re + (t - s) / rf = A / B with the integers A = s rf + (t - s) re <= 2^36 and B = re rf <= 2^60; FREX = t / (Vc c).
+ *   order    c ascending -- FREX descending --, compared EXACTLY: A B' against A' B as 96-bit integer products, never through a
+ *            floating-point number (two costs at ranks near 2^30 differ by less than a double resolves); equal costs by word id
+ *            ascending.  sorted((Fraction(A, B), w)) over the ranked words.
+ *   weight   0 <= s <= t, 1 <= t <= LLDA_FREX_MAX_T: s = 0 orders by rf alone, s = t by re alone.
+ *   outputs  top_idx, top_rank_f, top_rank_e [n_labels][n] int32: the word ids and their two ranks; entries beyond the number of
+ *            ranked words are -1 / 0 / 0.  1 <= n <= LLDA_FREX_MAX_N.
+ *   probe    [n_labels][m] int32 word ids or NULL, 0 <= m <= LLDA_FREX_MAX_N: probe_rank_f, probe_rank_e [n_labels][m] get the two
+ *            ranks of those words in that column; a probe outside 0 .. V-1 (-1: no word) or a word that is not ranked gives 0 / 0.
+ * Every output pointer may be NULL on its own.  All outputs are copies of inputs chosen by integer comparisons: bit-identical whatever
+ * the geometry.  The double a caller reports is computed on the host, (double)t * (double)B / ((double)Vc * (double)A), each step
+ * rounded; it is a report, never the key.
+ * One coalesced pass along the rank rows in chunks of LLDA_FREX_CHUNK words leaves partial lists in `scratch` (at least
+ * llda_frex_scratch_bytes(V, n_labels, n) = 12 x n x ceil(V / LLDA_FREX_CHUNK) x n_labels + 16 bytes, 8-byte aligned, contents
+ * irrelevant before and after); a second small launch merges them per column.  n_labels == 0 is a no-op.
+ * LLDA_E_BAD_ARG, before anything touches HIP: a NULL args; a struct_bytes other than sizeof(llda_frex_args); n_labels < 0 or
+ * > LLDA_MAX_K; V or Vc outside 1 .. 2^30; t outside 1 .. 64 or s outside 0 .. t; n outside 1 .. 16; m outside 0 .. 16; and with
+ * n_labels > 0: a NULL rank_f, rank_e or scratch, a misaligned pointer (8 bytes: scratch; 4: every other), scratch_bytes too small.
+ * llda_frex_scratch_bytes and llda_frex_struct_bytes are host only; the former returns LLDA_E_BAD_ARG for the same bad sizes. */
+#define LLDA_FREX_MAX_N 16
+#define LLDA_FREX_MAX_T 64
+#define LLDA_FREX_CHUNK 16384
+typedef struct llda_frex_args {
+    uint32_t struct_bytes;       /* sizeof(llda_frex_args)                                       */
+    int32_t  n_labels, n, m;
+    int32_t  s, t;
+    const int32_t *rank_f;       /* [dev] [n_labels][V]                                          */
+    const int32_t *rank_e;       /* [dev] [n_labels][V]                                          */
+    const int32_t *probe;        /* [dev] [n_labels][m] or NULL                                  */
+    int64_t  V, Vc;
+    int32_t *top_idx;            /* [dev] [n_labels][n] or NULL                                  */
+    int32_t *top_rank_f;         /* [dev] [n_labels][n] or NULL                                  */
+    int32_t *top_rank_e;         /* [dev] [n_labels][n] or NULL                                  */
+    int32_t *probe_rank_f;       /* [dev] [n_labels][m] or NULL                                  */
+    int32_t *probe_rank_e;       /* [dev] [n_labels][m] or NULL                                  */
+    void    *scratch;            /* [dev] work space                                             */
+    int64_t  scratch_bytes;
+} llda_frex_args;
+int llda_frex_struct_bytes(void);
+int64_t llda_frex_scratch_bytes(int64_t V, int32_t n_labels, int32_t n);
+int llda_frex_select(const llda_frex_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -356,6 +356,53 @@ class LabeledLDA(object):
         idx, score = self._label_words_device(n, lam, min_count, source)
         return idx.cpu().numpy(), score.cpu().numpy()
 
+    def _frex_device(self, n, weight, min_count, source, probe_n=0):
+        """``topics.frex_words`` on this model's phi (``source`` as in ``label_words``) with the words that occur at least
+        max(min_count, 1) times as candidates; probe_n > 0: the probes are every label's probe_n most probable candidate words"""
+        import torch
+        from . import topics
+        if source not in ("counts", "ph_hat"):
+            raise ValueError("source must be 'counts' or 'ph_hat'")
+        topics._check_n(n)
+        f = topics.frex_weight(weight)
+        sm = self._sampler
+        sm.check_status()
+        phi_t = sm.phi().t().contiguous() if source == "counts" else self._phi_t_device()
+        cand = (sm.word_totals() >= max(int(min_count), 1)).to(device=phi_t.device, dtype=torch.uint8)
+        probe = None
+        if probe_n:
+            probe = topics.scored_words(phi_t, self.K, probe_n, 1, cand.to(torch.float64))[0]
+        return f, topics.frex_words(phi_t, self.K, n, f, cand, probe)
+
+    def frex_words(self, n=10, weight=0.5, min_count=1, source="counts"):
+        """The n <= 16 FREX words of every label (Bischof and Airoldi 2012; the default labelling of the ``stm`` package): ((K, n)
+        int32 word ids, (K, n) float64 FREX) as numpy arrays, padded with -1 / NaN where a label ranks fewer than n words.
+        FREX = 1 / (w / F_e + (1 - w) / F_f): F_f is the ECDF of phi within the label at the word, F_e the ECDF of the word's
+        exclusivity phi_kw / sum_j phi_jw, both over the candidate words -- those that occur at least max(min_count, 1) times in the
+        corpus -- and w = weight, the weight on exclusivity, rounded to a fraction s / t with t <= 64 (``topics.frex_weight``).  Equal
+        values share the rank of the last of them (the ECDF itself; ``stm`` averages their ranks).  The order is FREX descending
+        decided on the exact integer fraction of the two ranks, then word id ascending (llda_ecdf_ranks, llda_frex_select); the
+        float64 is ``topics.frex_score``.  weight = 0 orders by phi, weight = 1 by exclusivity.  source as in ``label_words``.
+        n_k_v is replicated: no collective."""
+        from . import topics
+        f, (idx, rf, re, Vc) = self._frex_device(n, weight, min_count, source)
+        return idx.cpu().numpy(), topics.frex_score(re.cpu().numpy(), rf.cpu().numpy(), Vc, f.numerator, f.denominator)
+
+    def exclusivity(self, n=10, weight=0.7, min_count=1, source="counts"):
+        """Topic exclusivity (float64 [K]), the second axis of the "semantic coherence against exclusivity" plot of ``stm``: the
+        sum of FREX (weight on exclusivity ``weight``, as in ``frex_words``) over the label's n <= 16 most probable candidate words
+        -- the order of ``label_words(n, 1, min_count)``: phi descending, then word id ascending --, added in that order.  NaN for
+        a label with no ranked word.  n_k_v is replicated: no collective."""
+        from . import topics
+        f, (_, _, _, Vc, prf, pre) = self._frex_device(1, weight, min_count, source, probe_n=topics._check_n(n))
+        fx = topics.frex_score(pre.cpu().numpy(), prf.cpu().numpy(), Vc, f.numerator, f.denominator)
+        listed = ~np.isnan(fx)
+        total = np.zeros((self.K,), dtype=np.float64)
+        for j in range(fx.shape[1]):
+            total = total + np.where(listed[:, j], fx[:, j], 0.0)
+        total[~listed.any(axis=1)] = np.nan
+        return total
+
     def coherence(self, n=10, measure="umass", docs=None, lam=None, min_count=1):
         """Topic coherence of every label's n best words (float64 [K]; NaN for a label with fewer than two words or with a top
         word that the corpus never holds): measure = "umass" (Mimno et al. 2011) or "npmi", over the training corpus or, with

@@ -127,6 +127,21 @@ class LldaScoredArgs(ctypes.Structure):
                 ("n_nan", _c_p), ("scratch", _c_p), ("scratch_bytes", _c_i64)]
 
 
+class LldaEcdfArgs(ctypes.Structure):
+    """struct llda_ecdf_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("first", _c_i32), ("n_labels", _c_i32), ("chunk", _c_i32), ("mode", _c_i32),
+                ("mat", _c_p), ("cand", _c_p), ("V", _c_i64), ("ld", _c_i64), ("rank", _c_p), ("value", _c_p), ("n_cand", _c_p),
+                ("scratch", _c_p), ("scratch_bytes", _c_i64)]
+
+
+class LldaFrexArgs(ctypes.Structure):
+    """struct llda_frex_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("n_labels", _c_i32), ("n", _c_i32), ("m", _c_i32), ("s", _c_i32), ("t", _c_i32),
+                ("rank_f", _c_p), ("rank_e", _c_p), ("probe", _c_p), ("V", _c_i64), ("Vc", _c_i64), ("top_idx", _c_p),
+                ("top_rank_f", _c_p), ("top_rank_e", _c_p), ("probe_rank_f", _c_p), ("probe_rank_e", _c_p), ("scratch", _c_p),
+                ("scratch_bytes", _c_i64)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -136,7 +151,9 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_leftright_struct_bytes", "llda_left_to_right",
            "llda_nearest_struct_bytes", "llda_nearest_scratch_bytes", "llda_nearest_rows",
            "llda_label_struct_bytes", "llda_label_scratch_bytes", "llda_label_metrics", "llda_sets_struct_bytes", "llda_label_sets",
-           "llda_scored_struct_bytes", "llda_scored_words_scratch_bytes", "llda_scored_words")
+           "llda_scored_struct_bytes", "llda_scored_words_scratch_bytes", "llda_scored_words",
+           "llda_ecdf_struct_bytes", "llda_ecdf_scratch_bytes", "llda_ecdf_ranks",
+           "llda_frex_struct_bytes", "llda_frex_scratch_bytes", "llda_frex_select")
 
 _LIB = None
 
@@ -246,6 +263,18 @@ def lib():
     L.llda_scored_words_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
     L.llda_scored_words.restype = ctypes.c_int
     L.llda_scored_words.argtypes = [ctypes.POINTER(LldaScoredArgs), _c_p]
+    L.llda_ecdf_struct_bytes.restype = ctypes.c_int
+    L.llda_ecdf_struct_bytes.argtypes = []
+    L.llda_ecdf_scratch_bytes.restype = _c_i64
+    L.llda_ecdf_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
+    L.llda_ecdf_ranks.restype = ctypes.c_int
+    L.llda_ecdf_ranks.argtypes = [ctypes.POINTER(LldaEcdfArgs), _c_p]
+    L.llda_frex_struct_bytes.restype = ctypes.c_int
+    L.llda_frex_struct_bytes.argtypes = []
+    L.llda_frex_scratch_bytes.restype = _c_i64
+    L.llda_frex_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
+    L.llda_frex_select.restype = ctypes.c_int
+    L.llda_frex_select.argtypes = [ctypes.POINTER(LldaFrexArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -264,7 +293,8 @@ def lib():
         raise NativeError("LldaNearestArgs: binding has %d bytes, the library %d" % (ctypes.sizeof(LldaNearestArgs),
                                                                                      L.llda_nearest_struct_bytes()))
     for name, struct, size in (("LldaLabelArgs", LldaLabelArgs, L.llda_label_struct_bytes()), ("LldaSetsArgs", LldaSetsArgs, L.llda_sets_struct_bytes()),
-                               ("LldaScoredArgs", LldaScoredArgs, L.llda_scored_struct_bytes())):
+                               ("LldaScoredArgs", LldaScoredArgs, L.llda_scored_struct_bytes()),
+                               ("LldaEcdfArgs", LldaEcdfArgs, L.llda_ecdf_struct_bytes()), ("LldaFrexArgs", LldaFrexArgs, L.llda_frex_struct_bytes())):
         if size != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
@@ -487,6 +517,49 @@ def scored_words(V, K, n, a, scratch, *, n_kw=None, n_k=None, den=None, beta=0.0
                           int(V), int((0 if mat is None else mat.stride(0)) if ld is None else ld), float(beta), _ptr(top_idx),
                           _ptr(top_score), _ptr(n_nan), _ptr(scratch), int(scratch.numel() * scratch.element_size()))
     _launch(scratch, lib().llda_scored_words, "llda_scored_words", ctypes.byref(args))
+
+
+ECDF_MAX_V = 1 << 30          # LLDA_ECDF_MAX_V
+FREX_MAX_N = 16               # LLDA_FREX_MAX_N
+FREX_MAX_T = 64               # LLDA_FREX_MAX_T: the largest denominator of the weight
+FREX_CHUNK = 16384            # LLDA_FREX_CHUNK: words of a partial list of llda_frex_select
+
+
+def ecdf_scratch_bytes(V, n_labels, chunk=0):
+    """llda_ecdf_scratch_bytes: bytes of work space llda_ecdf_ranks needs (host only)."""
+    r = int(lib().llda_ecdf_scratch_bytes(int(V), int(n_labels), int(chunk)))
+    if r < 0:
+        check(r, "llda_ecdf_scratch_bytes(V=%d, n_labels=%d, chunk=%d)" % (V, n_labels, chunk))
+    return r
+
+
+def ecdf_ranks(mat, V, K, mode, first, n_labels, rank, scratch, *, ld=None, chunk=0, cand=None, value=None, n_cand=None):
+    """llda_ecdf_ranks on the current torch stream: mat (V, ld) float64 in reference topic order, cand (V,) uint8 or None; rank
+    (n_labels, V) int32, value (n_labels, V) float64 or None, n_cand (1,) int64 or None the outputs; scratch = a uint8 tensor of
+    ecdf_scratch_bytes(V, n_labels, chunk) bytes."""
+    a = LldaEcdfArgs(ctypes.sizeof(LldaEcdfArgs), int(K), int(first), int(n_labels), int(chunk), int(mode), _ptr(mat), _ptr(cand), int(V),
+                     int(mat.stride(0) if ld is None else ld), _ptr(rank), _ptr(value), _ptr(n_cand), _ptr(scratch),
+                     int(scratch.numel() * scratch.element_size()))
+    _launch(mat, lib().llda_ecdf_ranks, "llda_ecdf_ranks", ctypes.byref(a))
+
+
+def frex_scratch_bytes(V, n_labels, n):
+    """llda_frex_scratch_bytes: bytes of work space llda_frex_select needs (host only)."""
+    r = int(lib().llda_frex_scratch_bytes(int(V), int(n_labels), int(n)))
+    if r < 0:
+        check(r, "llda_frex_scratch_bytes(V=%d, n_labels=%d, n=%d)" % (V, n_labels, n))
+    return r
+
+
+def frex_select(rank_f, rank_e, V, Vc, n_labels, s, t, n, scratch, *, probe=None, m=0, top_idx=None, top_rank_f=None, top_rank_e=None,
+                probe_rank_f=None, probe_rank_e=None):
+    """llda_frex_select on the current torch stream: rank_f, rank_e (n_labels, V) int32; the weight s / t; top_idx, top_rank_f,
+    top_rank_e (n_labels, n) int32 and, with probe (n_labels, m) int32, probe_rank_f, probe_rank_e (n_labels, m) int32 the outputs,
+    each may be None; scratch = a uint8 tensor of frex_scratch_bytes(V, n_labels, n) bytes."""
+    a = LldaFrexArgs(ctypes.sizeof(LldaFrexArgs), int(n_labels), int(n), int(m), int(s), int(t), _ptr(rank_f), _ptr(rank_e), _ptr(probe),
+                     int(V), int(Vc), _ptr(top_idx), _ptr(top_rank_f), _ptr(top_rank_e), _ptr(probe_rank_f), _ptr(probe_rank_e),
+                     _ptr(scratch), int(scratch.numel() * scratch.element_size()))
+    _launch(scratch, lib().llda_frex_select, "llda_frex_select", ctypes.byref(a))
 
 
 def word_cooc(doc_off, word, D, V, K, n, memb_off, memb, co):

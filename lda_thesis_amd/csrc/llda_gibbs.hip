@@ -52,6 +52,8 @@
 //   kernel_nearest.hpp  llda_nearest_kernel, llda_nearest_merge_kernel   the n best rows of b per row of a: tiled fp64 product, selection in its epilogue
 //   kernel_label.hpp    llda_label_keys / _sort / _merge / _walk kernels   the documents of every label ranked: chunk sort in LDS, merge levels, one walk
 //                       llda_label_sets_kernel   per-label thresholds applied to every document: masks by ballot, tp / fp / fn
+//   kernel_ecdf.hpp     llda_ecdf_totals / _keys / _walk kernels   every word's ECDF rank within every topic, on kernel_label.hpp's sort
+//                       llda_frex_select_kernel, llda_frex_merge_kernel   the n best words of every topic by two ranks (FREX): exact 96-bit compares
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -91,6 +93,7 @@
 #include "kernel_leftright.hpp"
 #include "kernel_nearest.hpp"
 #include "kernel_label.hpp"
+#include "kernel_ecdf.hpp"
 
 namespace {
 
@@ -1288,6 +1291,102 @@ int llda_scored_words(const llda_scored_args *a, void *stream)
     else LLDA_SCORED(16)
 #undef LLDA_SCORED
 #undef LLDA_SCORED_MODE
+    return launched();
+}
+
+int llda_ecdf_struct_bytes(void) { return (int)sizeof(llda_ecdf_args); }
+int llda_frex_struct_bytes(void) { return (int)sizeof(llda_frex_args); }
+
+int64_t llda_ecdf_scratch_bytes(int64_t V, int32_t n_labels, int32_t chunk)
+{
+    const int64_t C = label_chunk(chunk);
+    if (V < 1 || V > LLDA_ECDF_MAX_V || n_labels < 0 || n_labels > LLDA_MAX_K || C == 0) return LLDA_E_BAD_ARG;
+    const int64_t Vp = (V + C - 1) / C * C;               // (Vp <= 2^30, n_labels < 2^13: the product stays below 2^48)
+    return 24 * Vp * n_labels + 8 * V + 16;
+}
+
+int llda_ecdf_ranks(const llda_ecdf_args *a, void *stream)
+{
+    static_assert(LLDA_ECDF_MAX_V == LLDA_LABEL_MAX_D, "the ECDF sort is the label sort");
+    if (!a || a->struct_bytes != sizeof(llda_ecdf_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->first < 0 || a->n_labels < 0 || a->first > a->K - a->n_labels || a->ld < a->K) return LLDA_E_BAD_ARG;
+    if (a->V < 1 || a->V > LLDA_ECDF_MAX_V || label_chunk(a->chunk) == 0 || (a->mode != 0 && a->mode != 1)) return LLDA_E_BAD_ARG;
+    if (a->n_labels == 0) return LLDA_OK;
+    if (!a->mat || !a->rank || !a->scratch || a->V > INT64_MAX / 8 / a->ld) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->mat, a->value, a->n_cand) || misaligned(7, a->scratch) || misaligned(3, a->rank)) return LLDA_E_BAD_ARG;
+    const int64_t need = llda_ecdf_scratch_bytes(a->V, a->n_labels, a->chunk);
+    if (need < 0 || a->scratch_bytes < need) return LLDA_E_BAD_ARG;
+    const int64_t C = label_chunk(a->chunk), Vp = (a->V + C - 1) / C * C, n = Vp * a->n_labels;
+    LabelParams S;                                        // the sort and the merge levels of llda_label_metrics, on these arrays
+    memset(&S, 0, sizeof S);
+    S.D = a->V; S.Dp = Vp; S.n_labels = a->n_labels;
+    S.key_a = static_cast<uint64_t *>(a->scratch);
+    S.key_b = S.key_a + n;
+    S.pay_a = reinterpret_cast<uint32_t *>(S.key_b + n);
+    S.pay_b = S.pay_a + n;
+    EcdfParams P;
+    memset(&P, 0, sizeof P);
+    P.mat = a->mat; P.cand = a->cand; P.V = a->V; P.ld = a->ld; P.Vp = Vp;
+    P.K = a->K; P.first = a->first; P.n_labels = a->n_labels; P.mode = a->mode;
+    P.tot = reinterpret_cast<double *>(S.pay_b + n);      // (24 n bytes in: 8-byte aligned)
+    P.key_a = S.key_a; P.pay_a = S.pay_a;
+    P.rank = a->rank; P.value = a->value; P.n_cand = a->n_cand;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned L = (unsigned)a->n_labels;
+    const int64_t rounds = (a->V + ECDF_WAVES - 1) / ECDF_WAVES;
+    hipLaunchKernelGGL(llda_ecdf_totals_kernel, dim3((unsigned)(rounds < (1 << 20) ? rounds : (1 << 20))), dim3(ECDF_WAVES * 64), 0, st, P);
+    hipLaunchKernelGGL(llda_ecdf_keys_kernel, dim3((unsigned)(Vp / 64), (L + 63) / 64), dim3(256), 0, st, P);
+    const bool small = C == LABEL_TEST_CHUNK;
+    if (small) hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Vp / C), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, S);
+    else hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_CHUNK>, dim3((unsigned)(Vp / C), L), dim3(LABEL_CHUNK / 8), 0, st, S);
+    int flip = 0;
+    for (int64_t R = C; R < Vp; R *= 2, flip ^= 1) {
+        S.run = R;
+        if (small) hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Vp / LABEL_TEST_CHUNK), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, S, flip);
+        else hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TILE>, dim3((unsigned)(Vp / LABEL_TILE), L), dim3(LABEL_TILE / 8), 0, st, S, flip);
+    }
+    P.key_sorted = flip ? S.key_b : S.key_a;
+    P.pay_sorted = flip ? S.pay_b : S.pay_a;
+    hipLaunchKernelGGL(llda_ecdf_walk_kernel, dim3(L), dim3(LABEL_WALK_NT), 0, st, P);
+    return launched();
+}
+
+int64_t llda_frex_scratch_bytes(int64_t V, int32_t n_labels, int32_t n)
+{
+    if (V < 1 || V > LLDA_ECDF_MAX_V || n_labels < 0 || n_labels > LLDA_MAX_K || n < 1 || n > LLDA_FREX_MAX_N) return LLDA_E_BAD_ARG;
+    return 12 * (int64_t)n * ((V + FREX_CHUNK - 1) / FREX_CHUNK) * n_labels + 16;    // (below 2^37)
+}
+
+int llda_frex_select(const llda_frex_args *a, void *stream)
+{
+    static_assert(FREX_CHUNK == LLDA_FREX_CHUNK && FREX_CHUNK % (64 * FREX_UNROLL) == 0, "kernel_ecdf.hpp restates the header");
+    if (!a || a->struct_bytes != sizeof(llda_frex_args)) return LLDA_E_BAD_ARG;
+    if (a->n_labels < 0 || a->n_labels > LLDA_MAX_K || a->V < 1 || a->V > LLDA_ECDF_MAX_V || a->Vc < 1 || a->Vc > LLDA_ECDF_MAX_V) return LLDA_E_BAD_ARG;
+    if (a->t < 1 || a->t > LLDA_FREX_MAX_T || a->s < 0 || a->s > a->t) return LLDA_E_BAD_ARG;
+    if (a->n < 1 || a->n > LLDA_FREX_MAX_N || a->m < 0 || a->m > LLDA_FREX_MAX_N) return LLDA_E_BAD_ARG;
+    if (a->n_labels == 0) return LLDA_OK;
+    if (!a->rank_f || !a->rank_e || !a->scratch) return LLDA_E_BAD_ARG;
+    if (misaligned(3, a->rank_f, a->rank_e, a->probe, a->top_idx, a->top_rank_f, a->top_rank_e, a->probe_rank_f, a->probe_rank_e)
+        || misaligned(7, a->scratch)) return LLDA_E_BAD_ARG;
+    const int64_t need = llda_frex_scratch_bytes(a->V, a->n_labels, a->n);
+    if (need < 0 || a->scratch_bytes < need) return LLDA_E_BAD_ARG;
+    FrexParams P;
+    memset(&P, 0, sizeof P);
+    P.rank_f = a->rank_f; P.rank_e = a->rank_e; P.probe = a->m > 0 ? a->probe : nullptr;
+    P.V = a->V; P.Vc = a->Vc; P.parts = (a->V + FREX_CHUNK - 1) / FREX_CHUNK;
+    P.n_labels = a->n_labels; P.n = a->n; P.m = a->m; P.s = a->s; P.u = a->t - a->s;
+    P.part = static_cast<int32_t *>(a->scratch);
+    P.top_idx = a->top_idx; P.top_rank_f = a->top_rank_f; P.top_rank_e = a->top_rank_e;
+    P.probe_rank_f = a->probe_rank_f; P.probe_rank_e = a->probe_rank_e;
+    const dim3 grid((unsigned)P.parts, (unsigned)a->n_labels), merge_grid((unsigned)a->n_labels);
+    hipStream_t st = (hipStream_t)stream;
+#define LLDA_FREX(N_) { hipLaunchKernelGGL(llda_frex_select_kernel<N_>, grid, dim3(64), 0, st, P); \
+                        hipLaunchKernelGGL(llda_frex_merge_kernel<N_>, merge_grid, dim3(64), 0, st, P); }
+    if (a->n <= 4) LLDA_FREX(4)
+    else if (a->n <= 10) LLDA_FREX(10)
+    else LLDA_FREX(16)
+#undef LLDA_FREX
     return launched();
 }
 

@@ -37,6 +37,15 @@ def build_parser():
     p.add_option("--relevance", dest="relevance", type="float", default=0.6, metavar="L",
                  help="the weight of --label-words between a word's probability under the label (1) and its lift over the corpus (0), "
                       "as in LDAvis; rounded to a fraction with a denominator of at most 8")
+    p.add_option("--frex-words", dest="frex_words", type="int", default=0, metavar="N",
+                 help="after the report: every label's N FREX words (Bischof and Airoldi 2012; llda_ecdf_ranks, llda_frex_select) next "
+                      "to its N most frequent ones")
+    p.add_option("--frex-weight", dest="frex_weight", type="float", default=None, metavar="W",
+                 help="the weight of --frex-words (default 0.5) and --exclusivity (default 0.7) on a word's exclusivity (1) against its "
+                      "probability under the label (0); rounded to a fraction with a denominator of at most 64")
+    p.add_option("--exclusivity", dest="exclusivity", type="int", default=0, metavar="N",
+                 help="after the report: topic exclusivity, the sum of FREX over every label's N most probable words, its mean and the "
+                      "five least exclusive labels")
     p.add_option("--heldout-perplexity", action="store_true", dest="heldout_perplexity", default=False,
                  help="after the report: perplexity of the held-out documents by document completion (every second word of a "
                       "document folded in, the others scored on the GPU: llda_heldout_loglik)")
@@ -197,6 +206,30 @@ def report_window_coherence(model, texts, n):
         print("  %-24s %10.3f  %s" % (names[k], coh[k], " ".join(model.v_to_w[int(v)] for v in idx[k] if v >= 0)))
 
 
+def report_frex_words(model, n, weight):
+    """every label's n FREX words (LabeledLDA.frex_words) next to its n most frequent ones"""
+    frequent, _ = model.top_words(n)
+    frex, _ = model.frex_words(n, weight)
+    names = list(model.labelmap.keys())
+    words = lambda row: " ".join(model.v_to_w[int(v)] for v in row if v >= 0)
+    print("-----------------------------------")
+    print("Label words (top %d): most frequent | FREX (weight %g):" % (n, weight))
+    for k, name in enumerate(names):
+        print("  %-24s %s | %s" % (name, words(frequent[k]), words(frex[k])))
+
+
+def report_exclusivity(model, n, weight):
+    """topic exclusivity of every label's n most probable words (LabeledLDA.exclusivity): the mean and the five lowest"""
+    ex = model.exclusivity(n, weight)
+    names = list(model.labelmap.keys())
+    ok = np.flatnonzero(~np.isnan(ex))
+    print("-----------------------------------")
+    print("Exclusivity (FREX weight %g, top %d words), mean over %d labels: %.3f" % (weight, n, len(ok), np.mean(ex[ok]) if len(ok) else float("nan")))
+    print("Least exclusive labels:")
+    for k in ok[np.argsort(ex[ok], kind="stable")[:5]]:
+        print("  %-24s %10.3f" % (names[k], ex[k]))
+
+
 def report_label_words(model, n, lam, coherence_n=0, window_n=0, texts=None):
     """every label's n most distinctive words (LabeledLDA.label_words) next to its n most frequent ones; coherence_n / window_n > 0: the
     mean UMass / C_V coherence of both kinds of list"""
@@ -271,6 +304,10 @@ def main(argv=None):
         report_window_coherence(model, train[0], opt.window_coherence)
     if opt.label_words:
         report_label_words(model, opt.label_words, opt.relevance, opt.coherence, opt.window_coherence, train[0])
+    if opt.frex_words:
+        report_frex_words(model, opt.frex_words, 0.5 if opt.frex_weight is None else opt.frex_weight)
+    if opt.exclusivity:
+        report_exclusivity(model, opt.exclusivity, 0.7 if opt.frex_weight is None else opt.frex_weight)
     if opt.heldout_perplexity:
         report_heldout(model, test, opt.it, opt.thinning)
     if opt.left_to_right:

@@ -22,6 +22,12 @@ Which words set a label apart is a float score, not a count: ``scored_words`` (`
 96-bit (score, word) keys, ``relevance_powers`` turns LDAvis's lam (Sievert and Shirley 2014) into the integer powers whose
 quotient has the order of relevance without a logarithm, and ``word_divisor`` builds the divisor from the words' totals.  Every
 score is a fixed sequence of IEEE multiplications and one division of one element: numpy restates it bit for bit.
+
+FREX (Bischof and Airoldi, "Summarizing topical content with word frequency and exclusivity", ICML 2012) scores a word by the
+harmonic mean of two RANKS within the topic -- of its probability and of its exclusivity phi_kw / sum_j phi_jw -- so it needs every
+topic's whole empirical distribution: ``ecdf_ranks`` (``llda_ecdf_ranks``: the segmented sort of ``llda_label_metrics`` over the
+vocabulary) leaves the integer ranks, ``frex_select`` (``llda_frex_select``) orders the words by the exact integer fraction the two
+ranks make, and ``frex_score`` is the float64 that is reported.  ``frex_words`` puts the three together in batches of labels.
 """
 import numpy as np
 
@@ -149,6 +155,155 @@ def scored_words(source, K, n, a=1, wdiv=None, *, n_k=None, beta=None, den=None,
             if t is not None:
                 t.record_stream(stream)
     return top_idx, top_score, n_nan
+
+
+def frex_weight(w):
+    """The weight on exclusivity as the fraction s / t ``llda_frex_select`` takes: ``Fraction(w).limit_denominator(64)``, 0 <= w <= 1
+    (a ``Fraction`` or an (s, t) pair passes through).  0.5 -> 1/2, 0.7 -> 7/10, 1 -> 1/1, 0 -> 0/1."""
+    from fractions import Fraction
+    if isinstance(w, tuple):
+        w = Fraction(int(w[0]), int(w[1]))
+    if not 0.0 <= float(w) <= 1.0:                       # (false for a NaN)
+        raise ValueError("the weight must be in 0 .. 1")
+    f = w if isinstance(w, Fraction) else Fraction(float(w))
+    return f.limit_denominator(_native.FREX_MAX_T)
+
+
+def frex_score(rank_e, rank_f, Vc, s, t):
+    """FREX = 1 / (omega / F_e + (1 - omega) / F_f) with omega = s / t and F = rank / Vc, as the float64 this project reports (numpy,
+    element-wise): (float(t) * float(B)) / (float(Vc) * float(A)) with the integers A = s rf + (t - s) re and B = re rf, each step
+    rounded; NaN where a rank is below 1.  A report: the order is decided on the integers (``frex_select``)."""
+    re, rf = np.asarray(rank_e).astype(np.int64), np.asarray(rank_f).astype(np.int64)
+    s, t = int(s), int(t)
+    A, B = s * rf + (t - s) * re, re * rf
+    ok = (re >= 1) & (rf >= 1)
+    out = np.full(A.shape, np.nan, dtype=np.float64)
+    out[ok] = (float(t) * B[ok].astype(np.float64)) / (float(int(Vc)) * A[ok].astype(np.float64))
+    return out
+
+
+def ecdf_ranks(mat, K, mode, cand=None, *, first=0, n_labels=None, chunk=0, value=False, stream=None):
+    """Every word's ECDF rank within the columns first .. first + n_labels - 1 (default: all K) of ``mat``, a float64 (V, ld >= K)
+    device tensor, word-major, reference topic order (``llda_ecdf_ranks``): device tensors (rank (n_labels, V) int32, n_cand (1,)
+    int64[, value (n_labels, V) float64 with value=True]).  mode 0 ranks the entry, mode 1 the entry over the row's total (the
+    exclusivity).  cand: uint8 / bool [V] (numpy or tensor) or None; a word outside it, or whose row total is not a positive
+    finite number, gets rank 0.  rank = #{candidates with a value <= the word's}.  Enqueues on ``stream`` (default: the current)."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    K, mode = int(K), int(mode)
+    if mode not in (0, 1):
+        raise ValueError("mode must be 0 or 1")
+    if not (isinstance(mat, torch.Tensor) and mat.is_cuda and mat.dim() == 2 and mat.dtype == torch.float64):
+        raise ValueError("mat must be a float64 (V, ld) tensor on the device")
+    if int(mat.shape[1]) < K or K < 1:
+        raise ValueError("the matrix needs at least K >= 1 columns")
+    if mat.stride(1) != 1 or mat.stride(0) < int(mat.shape[1]):
+        mat = mat.contiguous()
+    V, dev = int(mat.shape[0]), mat.device
+    n_labels = K - int(first) if n_labels is None else int(n_labels)
+    if first < 0 or n_labels < 0 or first + n_labels > K:
+        raise ValueError("first .. first + n_labels - 1 must lie in 0 .. K-1")
+    if cand is not None:
+        cand = torch.as_tensor(cand).to(device=dev).ne(0).to(torch.uint8).contiguous()
+        if tuple(cand.shape) != (V,):
+            raise ValueError("cand must hold one value per word")
+    nbytes = _native.ecdf_scratch_bytes(V, n_labels, chunk)
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(stream):
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        rank = torch.empty((n_labels, V), dtype=torch.int32, device=dev)
+        val = torch.empty((n_labels, V), dtype=torch.float64, device=dev) if value else None
+        n_cand = torch.zeros((1,), dtype=torch.int64, device=dev)
+        _native.ecdf_ranks(mat, V, K, mode, first, n_labels, rank, scratch, chunk=chunk, cand=cand, value=val, n_cand=n_cand)
+        for t in (mat, cand):
+            if t is not None:
+                t.record_stream(stream)
+    return (rank, n_cand, val) if value else (rank, n_cand)
+
+
+def frex_select(rank_f, rank_e, Vc, weight, n, probe=None, stream=None):
+    """The n best words of every column by FREX from two int32 (L, V) device tensors of ranks in 0 .. Vc (``llda_frex_select``):
+    device tensors (top_idx, top_rank_f, top_rank_e (L, n) int32, padded -1 / 0 / 0[, probe_rank_f, probe_rank_e (L, m) with
+    probe (L, m) int32 word ids, -1 = no word]).  weight: the weight on exclusivity, anything ``frex_weight`` takes.  The order is
+    exact: s / rank_e + (t - s) / rank_f ascending as integer fractions, then word id ascending."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    n = int(n)
+    if not 1 <= n <= _native.FREX_MAX_N:
+        raise ValueError("n must be in 1 .. %d" % _native.FREX_MAX_N)
+    f = frex_weight(weight)
+    for r in (rank_f, rank_e):
+        if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dim() == 2 and r.dtype == torch.int32 and r.is_contiguous()):
+            raise ValueError("rank_f and rank_e must be contiguous int32 (L, V) tensors on the device")
+    if rank_f.shape != rank_e.shape or rank_f.device != rank_e.device:
+        raise ValueError("rank_f and rank_e must have one shape and one device")
+    L, V, dev = int(rank_f.shape[0]), int(rank_f.shape[1]), rank_f.device
+    Vc = int(Vc)
+    if not 1 <= Vc <= _native.ECDF_MAX_V:
+        raise ValueError("Vc must be in 1 .. 2^30")
+    m = 0
+    if probe is not None:
+        probe = torch.as_tensor(probe).to(device=dev, dtype=torch.int32).contiguous()
+        if probe.dim() != 2 or int(probe.shape[0]) != L or not 1 <= int(probe.shape[1]) <= _native.FREX_MAX_N:
+            raise ValueError("probe must be (L, m) with m in 1 .. %d" % _native.FREX_MAX_N)
+        m = int(probe.shape[1])
+    nbytes = _native.frex_scratch_bytes(V, L, n)
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(stream):
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        out = [torch.empty((L, n), dtype=torch.int32, device=dev) for _ in range(3)]
+        pr = [torch.empty((L, m), dtype=torch.int32, device=dev) for _ in range(2)] if m else [None, None]
+        _native.frex_select(rank_f, rank_e, V, Vc, L, f.numerator, f.denominator, n, scratch, probe=probe, m=m, top_idx=out[0],
+                            top_rank_f=out[1], top_rank_e=out[2], probe_rank_f=pr[0], probe_rank_e=pr[1])
+        for t in (rank_f, rank_e, probe):
+            if t is not None:
+                t.record_stream(stream)
+    return tuple(out) + (tuple(pr) if m else ())
+
+
+def _frex_batch(V, K, free_bytes):
+    """how many labels one batch of ``frex_words`` ranks: a label costs the sort's 24 bytes a (padded) word and its two rank rows"""
+    Vp = -(-int(V) // _native.LABEL_CHUNK) * _native.LABEL_CHUNK
+    return int(max(1, min(int(K), (int(free_bytes) // 2) // (24 * Vp + 8 * int(V)))))
+
+
+def frex_words(phi_t, K, n, weight=0.5, cand=None, probe=None, batch=None):
+    """The n FREX words of every topic of ``phi_t``, a float64 (V, ld >= K) device tensor, word-major, reference topic order: device
+    tensors (top_idx, top_rank_f, top_rank_e (K, n) int32, Vc int[, probe_rank_f, probe_rank_e (K, m)]).  Two ``ecdf_ranks`` calls
+    (phi, and phi over the word's total: the exclusivity) and one ``frex_select`` per batch of labels; batch = None sizes the batches
+    to half of the device's free memory.  The batches change no bit.  No candidate word (Vc = 0): every list is padding."""
+    import torch
+    K, n = int(K), int(n)
+    V, dev = int(phi_t.shape[0]), phi_t.device
+    if batch is None:
+        batch = _frex_batch(V, K, torch.cuda.mem_get_info(dev)[0])
+    batch = max(1, int(batch))
+    if probe is not None:
+        probe = torch.as_tensor(probe).to(device=dev, dtype=torch.int32)
+    tops, probes, Vc = [], [], 0
+    for lo in range(0, K, batch):
+        L = min(batch, K - lo)
+        rank_f, n_cand = ecdf_ranks(phi_t, K, 0, cand, first=lo, n_labels=L)
+        rank_e, _ = ecdf_ranks(phi_t, K, 1, cand, first=lo, n_labels=L)
+        Vc = int(n_cand.item())
+        if Vc == 0:
+            tops.append((torch.full((L, n), -1, dtype=torch.int32, device=dev),) + tuple(torch.zeros((L, n), dtype=torch.int32, device=dev) for _ in range(2)))
+            if probe is not None:
+                probes.append(tuple(torch.zeros((L, int(probe.shape[1])), dtype=torch.int32, device=dev) for _ in range(2)))
+            continue
+        got = frex_select(rank_f, rank_e, Vc, weight, n, None if probe is None else probe[lo:lo + L])
+        tops.append(got[:3])
+        if probe is not None:
+            probes.append(got[3:])
+        del rank_f, rank_e
+    out = tuple(torch.cat([b[i] for b in tops]) for i in range(3)) + (Vc,)
+    if probe is not None:
+        out = out + tuple(torch.cat([b[i] for b in probes]) for i in range(2))
+    return out
 
 
 def _as_device_ids(top_idx, device=None):
