@@ -170,9 +170,9 @@ __global__ void __launch_bounds__(LABEL_WALK_NT) llda_ecdf_walk_kernel(const Ecd
 // whose costs differ by one part in 2^60 are still told apart, which no double does.
 //
 // The shape of kernel_scored.hpp, turned: the ranks lie [n_labels][V], so the lanes of ONE wavefront run along a column's row of
-// FREX_CHUNK words (coalesced 4-byte loads, four rounds in flight) and every lane keeps the best N of its words in registers --
-// (rf, re, word), 3 N registers; the padding has re = 0 and loses against everything.  Then the wavefront pops the best head of its
-// 64 lists n times (xor butterflies over the three words; word ids are unique, so one lane pops) and leaves one partial list of n.
+// FREX_CHUNK words (coalesced 4-byte loads, four rounds in flight) and every lane keeps the best N of its words in a TopList
+// (top_list.hpp) of (rf, re, word); the padding has re = 0 and loses against everything.  Then the wavefront pops the best head of
+// its 64 lists n times (word ids are unique within a column) and leaves one partial list of n.
 // llda_frex_merge_kernel: one wavefront per column, lanes over the partial lists, the same pop; its lanes below m look the probes up.
 // ---------------------------------------------------------------------------------------------
 constexpr int FREX_CHUNK = 16384;                        // words of a partial list
@@ -204,50 +204,15 @@ __device__ __forceinline__ bool frex_ranked(int32_t rf, int32_t re, int64_t Vc)
     return rf >= 1 && re >= 1 && rf <= Vc && re <= Vc;
 }
 
-template <int N>
-struct FrexList {
-    uint32_t rf[N], re[N], w[N];
-    __device__ __forceinline__ void clear()
-    {
-#pragma unroll
-        for (int j = 0; j < N; ++j) { rf[j] = 0; re[j] = 0; w[j] = FREX_PAD_ID; }
-    }
-    // sorted insertion, as scored_insert: every entry takes its better neighbour, the candidate, or stays
-    __device__ __forceinline__ void insert(int s, int u, uint32_t a, uint32_t b, uint32_t v)
-    {
-        bool bt[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) bt[j] = frex_better(s, u, a, b, v, rf[j], re[j], w[j]);
-#pragma unroll
-        for (int j = N - 1; j > 0; --j) {
-            rf[j] = bt[j - 1] ? rf[j - 1] : (bt[j] ? a : rf[j]);
-            re[j] = bt[j - 1] ? re[j - 1] : (bt[j] ? b : re[j]);
-            w[j] = bt[j - 1] ? w[j - 1] : (bt[j] ? v : w[j]);
-        }
-        rf[0] = bt[0] ? a : rf[0];
-        re[0] = bt[0] ? b : re[0];
-        w[0] = bt[0] ? v : w[0];
-    }
-    __device__ __forceinline__ bool admits(int s, int u, uint32_t a, uint32_t b, uint32_t v) const
-    {
-        return frex_better(s, u, a, b, v, rf[N - 1], re[N - 1], w[N - 1]);
-    }
-    // the best head of the wavefront's 64 lists, popped from the lane that holds it: the same (rf, re, w) in every lane
-    __device__ __forceinline__ void pop(int s, int u, uint32_t &a, uint32_t &b, uint32_t &v)
-    {
-        a = rf[0]; b = re[0]; v = w[0];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const uint32_t ya = (uint32_t)__shfl_xor((int)a, off, 64), yb = (uint32_t)__shfl_xor((int)b, off, 64);
-            const uint32_t yv = (uint32_t)__shfl_xor((int)v, off, 64);
-            if (frex_better(s, u, ya, yb, yv, a, b, v)) { a = ya; b = yb; v = yv; }
-        }
-        if (w[0] == v) {                                  // word ids are unique in a column: one lane pops (all once only padding is left)
-#pragma unroll
-            for (int j = 0; j + 1 < N; ++j) { rf[j] = rf[j + 1]; re[j] = re[j + 1]; w[j] = w[j + 1]; }
-            rf[N - 1] = 0; re[N - 1] = 0; w[N - 1] = FREX_PAD_ID;
-        }
-    }
+// (rf, re, word) as a list entry: w[0 .. 2]; the order carries the two weights
+struct FrexOrd {
+    static constexpr int Q = 0, W = 3;
+    typedef TopEntry<0, 3> E;
+    int s, u;
+    static __device__ __forceinline__ E entry(uint32_t rf, uint32_t re, uint32_t v) { return E{{0}, {rf, re, v}}; }
+    __device__ __forceinline__ E pad() const { return entry(0, 0, FREX_PAD_ID); }
+    __device__ __forceinline__ bool before(const E &a, const E &b) const { return frex_better(s, u, a.w[0], a.w[1], a.w[2], b.w[0], b.w[1], b.w[2]); }
+    __device__ __forceinline__ bool same(const E &a, const E &b) const { return a.w[2] == b.w[2]; }
 };
 
 template <int N>
@@ -257,9 +222,7 @@ __global__ void __launch_bounds__(64) llda_frex_select_kernel(const FrexParams P
     const int64_t w0 = (int64_t)blockIdx.x * FREX_CHUNK;
     const int64_t w1 = w0 + FREX_CHUNK < P.V ? w0 + FREX_CHUNK : P.V;
     const int32_t *rf = P.rank_f + (int64_t)l * P.V, *re = P.rank_e + (int64_t)l * P.V;
-    const int s = P.s, u = P.u;
-    FrexList<N> L;
-    L.clear();
+    TopList<N, FrexOrd> L(FrexOrd{P.s, P.u});
     for (int64_t w = w0 + lane; w < w1; w += 64 * FREX_UNROLL) {
         int32_t a[FREX_UNROLL], b[FREX_UNROLL];
 #pragma unroll
@@ -270,16 +233,14 @@ __global__ void __launch_bounds__(64) llda_frex_select_kernel(const FrexParams P
         }
 #pragma unroll
         for (int q = 0; q < FREX_UNROLL; ++q) {
-            const uint32_t v = (uint32_t)(w + 64 * q);
-            if (frex_ranked(a[q], b[q], P.Vc) && L.admits(s, u, (uint32_t)a[q], (uint32_t)b[q], v))
-                L.insert(s, u, (uint32_t)a[q], (uint32_t)b[q], v);
+            const FrexOrd::E e = FrexOrd::entry((uint32_t)a[q], (uint32_t)b[q], (uint32_t)(w + 64 * q));
+            if (frex_ranked(a[q], b[q], P.Vc) && L.admits(e)) L.insert(e);
         }
     }
     int32_t *out = P.part + ((int64_t)l * P.parts + blockIdx.x) * 3 * P.n;
     for (int i = 0; i < P.n; ++i) {
-        uint32_t a, b, v;
-        L.pop(s, u, a, b, v);
-        if (lane == 0) { out[i] = (int32_t)a; out[P.n + i] = (int32_t)b; out[2 * P.n + i] = (int32_t)v; }
+        const FrexOrd::E m = L.pop_wave();
+        if (lane == 0) { out[i] = (int32_t)m.w[0]; out[P.n + i] = (int32_t)m.w[1]; out[2 * P.n + i] = (int32_t)m.w[2]; }
     }
 }
 
@@ -287,26 +248,19 @@ template <int N>
 __global__ void __launch_bounds__(64) llda_frex_merge_kernel(const FrexParams P)
 {
     const int lane = threadIdx.x, l = blockIdx.x, n = P.n;
-    const int s = P.s, u = P.u;
-    FrexList<N> L;
-    L.clear();
+    TopList<N, FrexOrd> L(FrexOrd{P.s, P.u});
     for (int64_t part = lane; part < P.parts; part += 64) {
         const int32_t *in = P.part + ((int64_t)l * P.parts + part) * 3 * n;
-        for (int j = 0; j < n; ++j) {
-            const uint32_t a = (uint32_t)in[j], b = (uint32_t)in[n + j], v = (uint32_t)in[2 * n + j];
-            if (!L.admits(s, u, a, b, v)) break;          // (the partial list is in order: nothing behind it gets in either)
-            L.insert(s, u, a, b, v);
-        }
+        L.fold_sorted(n, [&](int j) { return FrexOrd::entry((uint32_t)in[j], (uint32_t)in[n + j], (uint32_t)in[2 * n + j]); });
     }
     for (int i = 0; i < n; ++i) {
-        uint32_t a, b, v;
-        L.pop(s, u, a, b, v);
+        const FrexOrd::E m = L.pop_wave();
         if (lane == 0) {
-            const bool real = b != 0;
+            const bool real = m.w[1] != 0;
             const int64_t at = (int64_t)l * n + i;
-            if (P.top_idx) P.top_idx[at] = real ? (int32_t)v : -1;
-            if (P.top_rank_f) P.top_rank_f[at] = real ? (int32_t)a : 0;
-            if (P.top_rank_e) P.top_rank_e[at] = real ? (int32_t)b : 0;
+            if (P.top_idx) P.top_idx[at] = real ? (int32_t)m.w[2] : -1;
+            if (P.top_rank_f) P.top_rank_f[at] = real ? (int32_t)m.w[0] : 0;
+            if (P.top_rank_e) P.top_rank_e[at] = real ? (int32_t)m.w[1] : 0;
         }
     }
     if (P.probe && lane < P.m) {

@@ -252,46 +252,42 @@ __global__ void __launch_bounds__(256) llda_nearest_kernel(const NearParams P)
     if (tid < NEAR_T && q0 + tid < P.Q) P.part_nan[(q0 + tid) * P.chunks + c] = (int64_t)nan_cnt[tid];
 }
 
-// sorted insertion into registers, as topw_insert: every entry takes its better neighbour, the candidate, or stays
-__device__ __forceinline__ void near_insert_regs(double (&S)[NEAR_MAX_N], int64_t (&I)[NEAR_MAX_N], double s, int64_t id)
-{
-#pragma unroll
-    for (int j = NEAR_MAX_N - 1; j > 0; --j) {
-        const bool up = near_beats(s, id, S[j - 1], I[j - 1]), here = near_beats(s, id, S[j], I[j]);
-        S[j] = up ? S[j - 1] : (here ? s : S[j]);
-        I[j] = up ? I[j - 1] : (here ? id : I[j]);
-    }
-    if (near_beats(s, id, S[0], I[0])) { S[0] = s; I[0] = id; }
-}
+// (score, id) as an entry of the merge kernel's TopList (top_list.hpp): the bits of the double, then the id
+struct NearOrd {
+    static constexpr int Q = 2, W = 0;
+    typedef TopEntry<2, 0> E;
+    static __device__ __forceinline__ double score(const E &e) { return __longlong_as_double((long long)e.q[0]); }
+    static __device__ __forceinline__ int64_t id(const E &e) { return (int64_t)e.q[1]; }
+    static __device__ __forceinline__ E entry(double s, int64_t id) { return E{{(uint64_t)__double_as_longlong(s), (uint64_t)id}, {0}}; }
+    __device__ __forceinline__ E pad() const { return entry(-INFINITY, NEAR_EMPTY); }
+    __device__ __forceinline__ bool before(const E &a, const E &b) const { return near_beats(score(a), id(a), score(b), id(b)); }
+    __device__ __forceinline__ bool same(const E &a, const E &b) const { return id(a) == id(b); }
+};
 
 __global__ void __launch_bounds__(64) llda_nearest_merge_kernel(const NearParams P)
 {
     const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (q >= P.Q) return;
     const int n = P.n;
-    double S[NEAR_MAX_N];
-    int64_t I[NEAR_MAX_N];
-#pragma unroll
-    for (int j = 0; j < NEAR_MAX_N; ++j) { S[j] = -INFINITY; I[j] = NEAR_EMPTY; }
+    TopList<NEAR_MAX_N, NearOrd> L;
     int64_t nans = 0;
     for (int64_t c = 0; c < P.chunks; ++c) {
         nans += P.part_nan[q * P.chunks + c];
         const double *ps = P.part_val + (q * P.chunks + c) * n;
         const int64_t *pi = P.part_idx + (q * P.chunks + c) * n;
         for (int p = 0; p < n; ++p) {
-            const double s = ps[p];
-            const int64_t id = pi[p];
+            const NearOrd::E e = NearOrd::entry(ps[p], pi[p]);
             // (the list is sorted: behind an empty place, or an entry that does not get in, nothing gets in either)
-            if (id == NEAR_EMPTY || !near_beats(s, id, S[NEAR_MAX_N - 1], I[NEAR_MAX_N - 1])) break;
-            near_insert_regs(S, I, s, id);
+            if (pi[p] == NEAR_EMPTY || !L.admits(e)) break;
+            L.insert(e);
         }
     }
 #pragma unroll
     for (int j = 0; j < NEAR_MAX_N; ++j)
         if (j < n) {
-            const bool real = I[j] != NEAR_EMPTY;
-            if (P.top_idx) P.top_idx[q * n + j] = real ? I[j] : -1;
-            if (P.top_val) P.top_val[q * n + j] = real ? S[j] : 0.0;
+            const int64_t id = NearOrd::id(L.at(j));
+            if (P.top_idx) P.top_idx[q * n + j] = id != NEAR_EMPTY ? id : -1;
+            if (P.top_val) P.top_val[q * n + j] = id != NEAR_EMPTY ? NearOrd::score(L.at(j)) : 0.0;
         }
     if (P.n_nan) P.n_nan[q] = nans;
 }

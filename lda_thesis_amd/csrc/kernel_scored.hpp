@@ -11,21 +11,20 @@ namespace {
 // is contracted (the translation unit is built with -ffp-contract=off).  Every output is therefore the result of the stated IEEE
 // operations on ONE element, and the result does not depend on the geometry.
 //
-// Key.  A float score does not fit llda_top_words' single 64-bit integer: the key is 96 bits, (score, word), kept as a double and a
-// uint32 side by side.  a is better than b when a.score > b.score, or the scores compare equal (-0 == +0) and a.word < b.word.  NaN
-// scores never enter a list (they are counted), so this is a total order over the entries of a column.  The padding is (-inf, all
-// ones): a word id never has bit 31 set, so a real -inf beats it.
+// Key.  A float score does not fit llda_top_words' single 64-bit integer: the key is 96 bits, (score, word), a TopList entry
+// (top_list.hpp): the double's bits and the id.  a is better than b when a.score > b.score, or the scores compare equal (-0 == +0) and
+// a.word < b.word.  NaN scores never enter a list (they are counted), so this is a total order over the entries of a column.  The
+// padding is (-inf, all ones): a word id never has bit 31 set, so a real -inf beats it.
 //
-// Pass 1, the shape of llda_top_words_kernel with TWO columns per thread instead of four: 2 * N * 3 = 96 list registers at N = 16.
-// One 8-byte load per row in counts mode, one 16-byte load in matrix mode (two 8-byte loads where the matrix is not 16-byte aligned
-// or its leading dimension is odd).  wdiv[row] is the same address for every lane of a row phase.  Every (row chunk, phase) leaves
-// its two lists and its two NaN counts in scratch: scores [parts][C][n], ids [parts][C][n], NaN counts [parts][C].
+// Pass 1, the shape of llda_top_words_kernel (its geometry, thread decode and unroll depth) with TWO columns per thread instead of
+// four: 2 * N * 3 = 96 list registers at N = 16.  One 8-byte load per row in counts mode, one 16-byte load in matrix mode (two 8-byte
+// loads where the matrix is not 16-byte aligned or its leading dimension is odd).  wdiv[row] is the same address for every lane of
+// a row phase.  Every (row chunk, phase) leaves its two lists and its two NaN counts in scratch: scores [parts][C][n], ids
+// [parts][C][n], NaN counts [parts][C].
 //
 // Pass 2: one wavefront per column -- a device position in counts mode (the padding returns at once), a topic in matrix mode --
 // folds the partial lists as llda_top_words_merge_kernel does and writes reference topic order.
 // ---------------------------------------------------------------------------------------------
-constexpr int SCORED_UNROLL = 4;
-constexpr int SCORED_MAX_PHASES = 4;                     // rows that share a workgroup when the row is short
 constexpr uint32_t SCORED_PAD_ID = 0xFFFFFFFFu;
 constexpr int SCORED_COUNTS = 0, SCORED_MATRIX = 1, SCORED_MATRIX_VEC = 2;
 
@@ -57,21 +56,16 @@ __device__ __forceinline__ bool scored_better(double s, uint32_t v, double t, ui
     return s > t || (s == t && v < w);
 }
 
-// sorted insertion into registers, as topw_insert: every entry takes its better neighbour, the candidate, or stays
-template <int N>
-__device__ __forceinline__ void scored_insert(double (&S)[N], uint32_t (&I)[N], double s, uint32_t v)
-{
-    bool b[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) b[j] = scored_better(s, v, S[j], I[j]);
-#pragma unroll
-    for (int j = N - 1; j > 0; --j) {
-        S[j] = b[j - 1] ? S[j - 1] : (b[j] ? s : S[j]);
-        I[j] = b[j - 1] ? I[j - 1] : (b[j] ? v : I[j]);
-    }
-    S[0] = b[0] ? s : S[0];
-    I[0] = b[0] ? v : I[0];
-}
+// (score, word) as a list entry: q[0] the bits of the double, w[0] the word id
+struct ScoredOrd {
+    static constexpr int Q = 1, W = 1;
+    typedef TopEntry<1, 1> E;
+    static __device__ __forceinline__ double score(const E &e) { return __longlong_as_double((long long)e.q[0]); }
+    static __device__ __forceinline__ E entry(double s, uint32_t v) { return E{{(uint64_t)__double_as_longlong(s)}, {v}}; }
+    __device__ __forceinline__ E pad() const { return entry(-__builtin_inf(), SCORED_PAD_ID); }
+    __device__ __forceinline__ bool before(const E &a, const E &b) const { return scored_better(score(a), a.w[0], score(b), b.w[0]); }
+    __device__ __forceinline__ bool same(const E &a, const E &b) const { return a.w[0] == b.w[0]; }
+};
 
 // P_a(x): a - 1 multiplications, left to right, each rounded
 __device__ __forceinline__ double scored_power(double x, int a)
@@ -82,28 +76,20 @@ __device__ __forceinline__ double scored_power(double x, int a)
 }
 
 template <int N>
-__device__ __forceinline__ void scored_consider(double (&S)[N], uint32_t (&I)[N], int &nan, double s, uint32_t v)
+__device__ __forceinline__ void scored_consider(TopList<N, ScoredOrd> &L, int &nan, double s, uint32_t v)
 {
+    const ScoredOrd::E e = ScoredOrd::entry(s, v);
     if (s != s) ++nan;
-    else if (scored_better(s, v, S[N - 1], I[N - 1])) scored_insert<N>(S, I, s, v);
+    else if (L.admits(e)) L.insert(e);
 }
 
 template <int N, int MODE>
 __global__ void __launch_bounds__(256) llda_scored_words_kernel(const ScoredParams P)
 {
-    const int tid = threadIdx.x;
     int lr, c;
-    if (P.rpb > 1) { lr = tid / P.cpr; c = tid - lr * P.cpr; }
-    else { lr = 0; c = (int)blockIdx.y * 256 + tid; }
-    if (lr >= P.rpb || c >= P.cpr) return;
-    const int64_t r0 = (int64_t)blockIdx.x * LLDA_TOPW_CHUNK_ROWS;
-    const int64_t r1 = r0 + LLDA_TOPW_CHUNK_ROWS < P.V ? r0 + LLDA_TOPW_CHUNK_ROWS : P.V;
-    double S[2][N];
-    uint32_t I[2][N];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int j = 0; j < N; ++j) { S[q][j] = -__builtin_inf(); I[q][j] = SCORED_PAD_ID; }
+    int64_t r0, r1;
+    if (!topw_thread(P.rpb, P.cpr, P.V, lr, c, r0, r1)) return;
+    TopList<N, ScoredOrd> L[2];
     int nan0 = 0, nan1 = 0;
     const int rpb = P.rpb, cpr = P.cpr, a = P.a;
     const bool divide = P.wdiv != nullptr;
@@ -113,11 +99,11 @@ __global__ void __launch_bounds__(256) llda_scored_words_kernel(const ScoredPara
         den0 = P.den ? P.den[2 * c] : (double)P.n_k[2 * c] + P.vbeta;
         den1 = P.den ? P.den[2 * c + 1] : (double)P.n_k[2 * c + 1] + P.vbeta;
     }
-    for (int64_t r = r0 + lr; r < r1; r += (int64_t)rpb * SCORED_UNROLL) {
-        double x0[SCORED_UNROLL], x1[SCORED_UNROLL], wd[SCORED_UNROLL];
-        int2 cnt[SCORED_UNROLL];
+    for (int64_t r = r0 + lr; r < r1; r += (int64_t)rpb * TOPW_UNROLL) {
+        double x0[TOPW_UNROLL], x1[TOPW_UNROLL], wd[TOPW_UNROLL];
+        int2 cnt[TOPW_UNROLL];
 #pragma unroll
-        for (int u = 0; u < SCORED_UNROLL; ++u) {
+        for (int u = 0; u < TOPW_UNROLL; ++u) {
             const int64_t rr = r + (int64_t)u * rpb;
             const bool in = rr < r1;
             x0[u] = x1[u] = 0.0;
@@ -136,7 +122,7 @@ __global__ void __launch_bounds__(256) llda_scored_words_kernel(const ScoredPara
             wd[u] = !in ? 0.0 : (divide ? P.wdiv[rr] : 1.0);
         }
 #pragma unroll
-        for (int u = 0; u < SCORED_UNROLL; ++u) {
+        for (int u = 0; u < TOPW_UNROLL; ++u) {
             const int64_t rr = r + (int64_t)u * rpb;
             if (wd[u] == 0.0) continue;                   // past the chunk, or a word that is not ranked (either sign of zero)
             if (MODE == SCORED_COUNTS) {
@@ -145,8 +131,8 @@ __global__ void __launch_bounds__(256) llda_scored_words_kernel(const ScoredPara
             }
             double s0 = scored_power(x0[u], a), s1 = scored_power(x1[u], a);
             if (divide) { s0 = s0 / wd[u]; s1 = s1 / wd[u]; }
-            scored_consider<N>(S[0], I[0], nan0, s0, (uint32_t)rr);
-            scored_consider<N>(S[1], I[1], nan1, s1, (uint32_t)rr);
+            scored_consider<N>(L[0], nan0, s0, (uint32_t)rr);
+            scored_consider<N>(L[1], nan1, s1, (uint32_t)rr);
         }
     }
     const int64_t part = (int64_t)blockIdx.x * rpb + lr;
@@ -157,7 +143,7 @@ __global__ void __launch_bounds__(256) llda_scored_words_kernel(const ScoredPara
     for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int j = 0; j < N; ++j)
-            if (j < P.n) { ds[q * P.n + j] = S[q][j]; di[q * P.n + j] = I[q][j]; }
+            if (j < P.n) { ds[q * P.n + j] = ScoredOrd::score(L[q].at(j)); di[q * P.n + j] = L[q].at(j).w[0]; }
     P.part_nan[col] = nan0;
     P.part_nan[col + 1] = nan1;
 }
@@ -169,45 +155,24 @@ __global__ void __launch_bounds__(64) llda_scored_merge_kernel(const ScoredParam
     const int k = P.n_kw ? wide_topic_of(P.leaf_start, P.leaf_len, P.G, P.T, col) : col;
     if (k < 0) return;                                    // a position of the padding: its lists are never read
     const int n = P.n;
-    double S[N];
-    uint32_t I[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) { S[j] = -__builtin_inf(); I[j] = SCORED_PAD_ID; }
+    TopList<N, ScoredOrd> L;
     int nan = 0;
     for (int64_t part = lane; part < P.parts; part += 64) {
         const int64_t at = part * P.C + col;
         nan += P.part_nan[at];
         const double *ss = P.part_score + at * n;
         const uint32_t *si = P.part_id + at * n;
-        for (int j = 0; j < n; ++j) {
-            const double s = ss[j];
-            const uint32_t v = si[j];
-            if (!scored_better(s, v, S[N - 1], I[N - 1])) break;   // (the partial list descends: nothing behind it gets in either)
-            scored_insert<N>(S, I, s, v);
-        }
+        L.fold_sorted(n, [&](int j) { return ScoredOrd::entry(ss[j], si[j]); });
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) nan += __shfl_xor(nan, off, 64);
     if (lane == 0 && P.n_nan) P.n_nan[k] = nan;
     for (int i = 0; i < n; ++i) {
-        double ms = S[0];
-        uint32_t mv = I[0];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double ys = __shfl_xor(ms, off, 64);
-            const uint32_t yv = (uint32_t)__shfl_xor((int)mv, off, 64);
-            if (scored_better(ys, yv, ms, mv)) { ms = ys; mv = yv; }
-        }
-        if (I[0] == mv) {                                 // word ids are unique in a column: one lane pops (all once only padding is left)
-#pragma unroll
-            for (int j = 0; j + 1 < N; ++j) { S[j] = S[j + 1]; I[j] = I[j + 1]; }
-            S[N - 1] = -__builtin_inf();
-            I[N - 1] = SCORED_PAD_ID;
-        }
+        const ScoredOrd::E m = L.pop_wave();
         if (lane == 0) {
-            const bool real = mv != SCORED_PAD_ID;
-            if (P.top_idx) P.top_idx[(int64_t)k * n + i] = real ? (int32_t)mv : -1;
-            if (P.top_score) P.top_score[(int64_t)k * n + i] = real ? ms : __longlong_as_double(0x7ff8000000000000ll);
+            const bool real = m.w[0] != SCORED_PAD_ID;
+            if (P.top_idx) P.top_idx[(int64_t)k * n + i] = real ? (int32_t)m.w[0] : -1;
+            if (P.top_score) P.top_score[(int64_t)k * n + i] = real ? ScoredOrd::score(m) : __longlong_as_double(0x7ff8000000000000ll);
         }
     }
 }

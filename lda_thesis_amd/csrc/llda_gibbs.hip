@@ -40,6 +40,8 @@
 //   kernel_hist.hpp     llda_count_hist_kernel    counts of counts of n_dk / n_kw (the estimate of alpha and beta)
 //   kernel_rank.hpp     llda_rank_labels_kernel   top-n labels and the harness metrics' ingredients from one sort per document
 //   kernel_wide.hpp     the general path for K with more than 8 pairwise leaves (one wavefront per document)
+//   top_list.hpp        TopList<N, Ord>   the N best entries under a strict total order, sorted in registers: insertion, the fold of
+//                                         sorted partial lists, the pop across a wavefront (the four selections below; a host test too)
 //   kernel_topwords.hpp llda_top_words_kernel, llda_top_words_merge_kernel   the n best words of every topic, by count
 //   kernel_scored.hpp   llda_scored_words_kernel, llda_scored_merge_kernel   the n best words of every topic by a float64 score: 96-bit (score, word) keys
 //   kernel_cooc.hpp     llda_word_cooc_kernel, llda_word_cooc_agg_kernel   document and co-document frequencies of the listed words (topic coherence)
@@ -83,6 +85,7 @@
 #include "kernel_hist.hpp"
 #include "kernel_rank.hpp"
 #include "kernel_wide.hpp"
+#include "top_list.hpp"
 #include "kernel_topwords.hpp"
 #include "kernel_scored.hpp"
 #include "kernel_cooc.hpp"
@@ -177,6 +180,15 @@ int visit_int(int v, F &&f)
     return rc;
 }
 
+// f with the smallest of Ns (ascending) that is >= n, LLDA_E_BAD_K when none is
+template <int... Ns, typename F>
+int visit_at_least(int n, F &&f)
+{
+    int b = -1;
+    (void)((n <= Ns && ((b = Ns), true)) || ...);
+    return visit_int<Ns...>(b, f);
+}
+
 template <typename F>
 int visit_bool(bool b, F &&f)
 {
@@ -191,6 +203,13 @@ int visit_layout(int G, int T, F &&f)
         if constexpr (g.value == 8) return visit_int<1, 2, 4, 8, 12, 16>(T, [&](auto t) { return f(g, t); });
         else return visit_int<12, 16>(T, [&](auto t) { return f(g, t); });
     });
+}
+
+// the leaf table of the pairwise sum, into the parameters of a kernel that maps positions to topics
+template <typename Params>
+void copy_leaves(const llda_layout &L, Params &P)
+{
+    for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { P.leaf_start[p] = L.leaf_start[p]; P.leaf_len[p] = L.leaf_len[p]; }
 }
 
 // The layout of K (128 KB of tables): built once per host thread and K, not once per call.
@@ -875,15 +894,20 @@ int llda_rank_labels(const llda_rank_args *a, void *stream)
     return launched();
 }
 
-// the geometry of llda_top_words: row phases of a workgroup, workgroups across a row, partial lists per column
-static void topw_geometry(const llda_layout &L, int64_t V, int32_t &rpb, int32_t &col_blocks, int64_t &chunks)
+// the geometry of a row-chunk pass (llda_top_words, llda_scored_words) over `cols` columns, `per` of them to a thread: column chunks
+// of a row, row phases of a workgroup, workgroups across a row, row chunks.  A column has chunks * rpb partial lists.
+struct RowChunkGeometry { int32_t cpr, rpb, col_blocks; int64_t chunks; };
+
+static RowChunkGeometry row_chunk_geometry(int32_t cols, int32_t per, int64_t V)
 {
-    const int cpr = L.KP / 4;
-    rpb = 256 / cpr;
-    if (rpb < 1) rpb = 1;
-    if (rpb > TOPW_MAX_PHASES) rpb = TOPW_MAX_PHASES;
-    col_blocks = (cpr + 255) / 256;
-    chunks = (V + LLDA_TOPW_CHUNK_ROWS - 1) / LLDA_TOPW_CHUNK_ROWS;
+    RowChunkGeometry g;
+    g.cpr = (cols + per - 1) / per;
+    g.rpb = 256 / g.cpr;
+    if (g.rpb < 1) g.rpb = 1;
+    if (g.rpb > TOPW_MAX_PHASES) g.rpb = TOPW_MAX_PHASES;
+    g.col_blocks = (g.cpr + 255) / 256;
+    g.chunks = (V + LLDA_TOPW_CHUNK_ROWS - 1) / LLDA_TOPW_CHUNK_ROWS;
+    return g;
 }
 
 int64_t llda_top_words_scratch_bytes(int64_t V, int32_t K, int32_t n)
@@ -892,10 +916,8 @@ int64_t llda_top_words_scratch_bytes(int64_t V, int32_t K, int32_t n)
     int rc;
     const llda_layout *Lp = layout_of(K, &rc);
     if (rc) return rc;
-    int32_t rpb, col_blocks;
-    int64_t chunks;
-    topw_geometry(*Lp, V, rpb, col_blocks, chunks);
-    return chunks * rpb * Lp->KP * n * (int64_t)sizeof(uint64_t);
+    const RowChunkGeometry g = row_chunk_geometry(Lp->KP, 4, V);
+    return g.chunks * g.rpb * Lp->KP * n * (int64_t)sizeof(uint64_t);
 }
 
 int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t *top_idx, int32_t *top_cnt, void *scratch,
@@ -909,27 +931,22 @@ int llda_top_words(const int32_t *n_kw, int64_t V, int32_t K, int32_t n, int32_t
     if (misaligned(15, n_kw) || misaligned(7, scratch) || misaligned(3, top_idx, top_cnt)) return LLDA_E_BAD_ARG;
     TopwParams P;
     memset(&P, 0, sizeof P);
-    int32_t col_blocks;
-    int64_t chunks;
-    topw_geometry(L, V, P.rpb, col_blocks, chunks);
-    P.parts = chunks * P.rpb;
+    const RowChunkGeometry g = row_chunk_geometry(L.KP, 4, V);
+    P.rpb = g.rpb;
+    P.parts = g.chunks * g.rpb;
     if (scratch_bytes < P.parts * L.KP * n * (int64_t)sizeof(uint64_t)) return LLDA_E_BAD_ARG;
     P.n_kw = reinterpret_cast<const int4 *>(n_kw);
-    P.V = V; P.cpr = L.KP / 4; P.n = n; P.KP = L.KP; P.G = L.G; P.T = L.T; P.K = L.K;
+    P.V = V; P.cpr = g.cpr; P.n = n; P.KP = L.KP; P.G = L.G; P.T = L.T; P.K = L.K;
     P.scratch = static_cast<uint64_t *>(scratch);
     P.top_idx = top_idx; P.top_cnt = top_cnt;
-    for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { P.leaf_start[p] = L.leaf_start[p]; P.leaf_len[p] = L.leaf_len[p]; }
-    const dim3 grid((unsigned)chunks, (unsigned)col_blocks), merge_grid((unsigned)L.KP);
+    copy_leaves(L, P);
+    const dim3 grid((unsigned)g.chunks, (unsigned)g.col_blocks), merge_grid((unsigned)L.KP);
     hipStream_t st = (hipStream_t)stream;
-#define LLDA_TOPW(N_) { hipLaunchKernelGGL(llda_top_words_kernel<N_>, grid, dim3(256), 0, st, P); \
-                        hipLaunchKernelGGL(llda_top_words_merge_kernel<N_>, merge_grid, dim3(64), 0, st, P); }
-    if (n <= 2) LLDA_TOPW(2)
-    else if (n <= 4) LLDA_TOPW(4)
-    else if (n <= 8) LLDA_TOPW(8)
-    else if (n <= 10) LLDA_TOPW(10)
-    else LLDA_TOPW(16)
-#undef LLDA_TOPW
-    return launched();
+    return visit_at_least<2, 4, 8, 10, 16>(n, [&](auto N) {
+        hipLaunchKernelGGL(llda_top_words_kernel<N.value>, grid, dim3(256), 0, st, P);
+        hipLaunchKernelGGL(llda_top_words_merge_kernel<N.value>, merge_grid, dim3(64), 0, st, P);
+        return launched();
+    });
 }
 
 int llda_word_cooc(const int64_t *doc_off, const int32_t *word, int64_t D, int64_t V, int32_t K, int32_t n,
@@ -1148,6 +1165,23 @@ int64_t llda_label_scratch_bytes(int64_t D, int32_t n_labels, int32_t chunk)
     return 24 * Dp * n_labels + 16;                       // (never 0: a caller's allocation always has an address)
 }
 
+// llda_label_sort_kernel over chunks of C, then the merge levels, on P's four arrays (Dp positions by n_labels).  Returns 0 when
+// key_a / pay_a hold the sorted rows, 1 when key_b / pay_b do.
+static int label_sort(LabelParams &P, int64_t C, hipStream_t st)
+{
+    const unsigned L = (unsigned)P.n_labels;
+    const bool small = C == LABEL_TEST_CHUNK;
+    if (small) hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(P.Dp / C), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, P);
+    else hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_CHUNK>, dim3((unsigned)(P.Dp / C), L), dim3(LABEL_CHUNK / 8), 0, st, P);
+    int flip = 0;
+    for (int64_t R = C; R < P.Dp; R *= 2, flip ^= 1) {
+        P.run = R;
+        if (small) hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(P.Dp / LABEL_TEST_CHUNK), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, P, flip);
+        else hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TILE>, dim3((unsigned)(P.Dp / LABEL_TILE), L), dim3(LABEL_TILE / 8), 0, st, P, flip);
+    }
+    return flip;
+}
+
 int llda_label_metrics(const llda_label_args *a, void *stream)
 {
     static_assert(LABEL_CHUNK == LLDA_LABEL_CHUNK && LABEL_TEST_CHUNK == LLDA_LABEL_TEST_CHUNK, "kernel_label.hpp restates the header");
@@ -1176,15 +1210,7 @@ int llda_label_metrics(const llda_label_args *a, void *stream)
     hipStream_t st = (hipStream_t)stream;
     const unsigned L = (unsigned)a->n_labels;
     hipLaunchKernelGGL(llda_label_keys_kernel, dim3((unsigned)(Dp / 64), (L + 63) / 64), dim3(256), 0, st, P);
-    const bool small = C == LABEL_TEST_CHUNK;
-    if (small) hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Dp / C), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, P);
-    else hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_CHUNK>, dim3((unsigned)(Dp / C), L), dim3(LABEL_CHUNK / 8), 0, st, P);
-    int flip = 0;
-    for (int64_t R = C; R < Dp; R *= 2, flip ^= 1) {
-        P.run = R;
-        if (small) hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Dp / LABEL_TEST_CHUNK), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, P, flip);
-        else hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TILE>, dim3((unsigned)(Dp / LABEL_TILE), L), dim3(LABEL_TILE / 8), 0, st, P, flip);
-    }
+    const int flip = label_sort(P, C, st);
     P.key_sorted = flip ? P.key_b : P.key_a;
     P.pay_sorted = flip ? P.pay_b : P.pay_a;
     hipLaunchKernelGGL(llda_label_walk_kernel, dim3(L), dim3(LABEL_WALK_NT), 0, st, P);
@@ -1219,23 +1245,11 @@ int llda_label_sets(const llda_sets_args *a, void *stream)
 
 int llda_scored_struct_bytes(void) { return (int)sizeof(llda_scored_args); }
 
-// the geometry of llda_scored_words over `cols` columns (KP in counts mode, K in matrix mode) and the scratch it leaves behind
-struct ScoredGeometry { int32_t cpr, rpb, col_blocks; int64_t chunks; };
+// the scratch of llda_scored_words over `cols` columns (KP in counts mode, K in matrix mode), two to a thread.  Per (part, column):
+// n scores, n word ids, one NaN count (2 * cpr columns: a multiple of 8 bytes)
+static RowChunkGeometry scored_geometry(int32_t cols, int64_t V) { return row_chunk_geometry(cols, 2, V); }
 
-static ScoredGeometry scored_geometry(int32_t cols, int64_t V)
-{
-    ScoredGeometry g;
-    g.cpr = (cols + 1) / 2;
-    g.rpb = 256 / g.cpr;
-    if (g.rpb < 1) g.rpb = 1;
-    if (g.rpb > SCORED_MAX_PHASES) g.rpb = SCORED_MAX_PHASES;
-    g.col_blocks = (g.cpr + 255) / 256;
-    g.chunks = (V + LLDA_TOPW_CHUNK_ROWS - 1) / LLDA_TOPW_CHUNK_ROWS;
-    return g;
-}
-
-// per (part, column): n scores, n word ids, one NaN count (2 * cpr columns: a multiple of 8 bytes)
-static int64_t scored_bytes(const ScoredGeometry &g, int32_t n) { return g.chunks * g.rpb * (2 * (int64_t)g.cpr) * (12 * n + 4); }
+static int64_t scored_bytes(const RowChunkGeometry &g, int32_t n) { return g.chunks * g.rpb * (2 * (int64_t)g.cpr) * (12 * n + 4); }
 
 int64_t llda_scored_words_scratch_bytes(int64_t V, int32_t K, int32_t n)
 {
@@ -1262,7 +1276,7 @@ int llda_scored_words(const llda_scored_args *a, void *stream)
     const llda_layout *Lp = layout_of(a->K, &rc);
     if (rc) return rc;
     const llda_layout &L = *Lp;
-    const ScoredGeometry g = scored_geometry(counts ? L.KP : a->K, a->V);
+    const RowChunkGeometry g = scored_geometry(counts ? L.KP : a->K, a->V);
     if (a->scratch_bytes < scored_bytes(g, a->n)) return LLDA_E_BAD_ARG;
     ScoredParams P;
     memset(&P, 0, sizeof P);
@@ -1276,22 +1290,18 @@ int llda_scored_words(const llda_scored_args *a, void *stream)
     P.part_id = reinterpret_cast<uint32_t *>(P.part_score + lists);
     P.part_nan = reinterpret_cast<int32_t *>(P.part_id + lists);
     P.top_idx = a->top_idx; P.top_score = a->top_score; P.n_nan = a->n_nan;
-    for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { P.leaf_start[p] = L.leaf_start[p]; P.leaf_len[p] = L.leaf_len[p]; }
+    copy_leaves(L, P);
     const dim3 grid((unsigned)g.chunks, (unsigned)g.col_blocks), merge_grid((unsigned)(counts ? L.KP : a->K));
     hipStream_t st = (hipStream_t)stream;
     // 16-byte loads of a matrix row pair need the base 16-byte aligned and an even leading dimension
     const int mode = counts ? SCORED_COUNTS : (!misaligned(15, a->mat) && !(a->ld & 1)) ? SCORED_MATRIX_VEC : SCORED_MATRIX;
-#define LLDA_SCORED_MODE(N_, M_) hipLaunchKernelGGL((llda_scored_words_kernel<N_, M_>), grid, dim3(256), 0, st, P)
-#define LLDA_SCORED(N_) { if (mode == SCORED_COUNTS) LLDA_SCORED_MODE(N_, SCORED_COUNTS); \
-                          else if (mode == SCORED_MATRIX_VEC) LLDA_SCORED_MODE(N_, SCORED_MATRIX_VEC); \
-                          else LLDA_SCORED_MODE(N_, SCORED_MATRIX); \
-                          hipLaunchKernelGGL(llda_scored_merge_kernel<N_>, merge_grid, dim3(64), 0, st, P); }
-    if (a->n <= 4) LLDA_SCORED(4)
-    else if (a->n <= 10) LLDA_SCORED(10)
-    else LLDA_SCORED(16)
-#undef LLDA_SCORED
-#undef LLDA_SCORED_MODE
-    return launched();
+    return visit_at_least<4, 10, 16>(a->n, [&](auto N) {
+        return visit_int<SCORED_COUNTS, SCORED_MATRIX, SCORED_MATRIX_VEC>(mode, [&](auto M) {
+            hipLaunchKernelGGL((llda_scored_words_kernel<N.value, M.value>), grid, dim3(256), 0, st, P);
+            hipLaunchKernelGGL(llda_scored_merge_kernel<N.value>, merge_grid, dim3(64), 0, st, P);
+            return launched();
+        });
+    });
 }
 
 int llda_ecdf_struct_bytes(void) { return (int)sizeof(llda_ecdf_args); }
@@ -1337,15 +1347,7 @@ int llda_ecdf_ranks(const llda_ecdf_args *a, void *stream)
     const int64_t rounds = (a->V + ECDF_WAVES - 1) / ECDF_WAVES;
     hipLaunchKernelGGL(llda_ecdf_totals_kernel, dim3((unsigned)(rounds < (1 << 20) ? rounds : (1 << 20))), dim3(ECDF_WAVES * 64), 0, st, P);
     hipLaunchKernelGGL(llda_ecdf_keys_kernel, dim3((unsigned)(Vp / 64), (L + 63) / 64), dim3(256), 0, st, P);
-    const bool small = C == LABEL_TEST_CHUNK;
-    if (small) hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Vp / C), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, S);
-    else hipLaunchKernelGGL(llda_label_sort_kernel<LABEL_CHUNK>, dim3((unsigned)(Vp / C), L), dim3(LABEL_CHUNK / 8), 0, st, S);
-    int flip = 0;
-    for (int64_t R = C; R < Vp; R *= 2, flip ^= 1) {
-        S.run = R;
-        if (small) hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TEST_CHUNK>, dim3((unsigned)(Vp / LABEL_TEST_CHUNK), L), dim3(LABEL_TEST_CHUNK / 8), 0, st, S, flip);
-        else hipLaunchKernelGGL(llda_label_merge_kernel<LABEL_TILE>, dim3((unsigned)(Vp / LABEL_TILE), L), dim3(LABEL_TILE / 8), 0, st, S, flip);
-    }
+    const int flip = label_sort(S, C, st);
     P.key_sorted = flip ? S.key_b : S.key_a;
     P.pay_sorted = flip ? S.pay_b : S.pay_a;
     hipLaunchKernelGGL(llda_ecdf_walk_kernel, dim3(L), dim3(LABEL_WALK_NT), 0, st, P);
@@ -1381,13 +1383,11 @@ int llda_frex_select(const llda_frex_args *a, void *stream)
     P.probe_rank_f = a->probe_rank_f; P.probe_rank_e = a->probe_rank_e;
     const dim3 grid((unsigned)P.parts, (unsigned)a->n_labels), merge_grid((unsigned)a->n_labels);
     hipStream_t st = (hipStream_t)stream;
-#define LLDA_FREX(N_) { hipLaunchKernelGGL(llda_frex_select_kernel<N_>, grid, dim3(64), 0, st, P); \
-                        hipLaunchKernelGGL(llda_frex_merge_kernel<N_>, merge_grid, dim3(64), 0, st, P); }
-    if (a->n <= 4) LLDA_FREX(4)
-    else if (a->n <= 10) LLDA_FREX(10)
-    else LLDA_FREX(16)
-#undef LLDA_FREX
-    return launched();
+    return visit_at_least<4, 10, 16>(a->n, [&](auto N) {
+        hipLaunchKernelGGL(llda_frex_select_kernel<N.value>, grid, dim3(64), 0, st, P);
+        hipLaunchKernelGGL(llda_frex_merge_kernel<N.value>, merge_grid, dim3(64), 0, st, P);
+        return launched();
+    });
 }
 
 int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab_mask, const int32_t *n_dk,
@@ -1420,7 +1420,7 @@ int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab
 static void readout_layout(const llda_layout &L, RParams &P)
 {
     P.K = L.K; P.KP = L.KP; P.T = L.T;
-    for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { P.leaf_start[p] = L.leaf_start[p]; P.leaf_len[p] = L.leaf_len[p]; }
+    copy_leaves(L, P);
     fill_schedule(L, P.last_leaf, P.tail, P.tail_row, P.n_rounds, P.xor_tree, P.rounds_pk);
 }
 
@@ -1456,7 +1456,7 @@ int llda_readout_theta(const int32_t *n_dk, const uint16_t *lab_mask, int64_t D,
         memset(&W, 0, sizeof W);
         W.n_dk = n_dk; W.lab_mask = lab_mask; W.out = out; W.D = D; W.K = L.K; W.mode = mode; W.alpha = alpha;
         W.keep = keep; W.share = share;
-        for (int p = 0; p < LLDA_MAX_WIDE_LEAVES; ++p) { W.leaf_start[p] = L.leaf_start[p]; W.leaf_len[p] = L.leaf_len[p]; }
+        copy_leaves(L, W);
         fill_wide(L, W.w);
         const size_t lds = (size_t)L.KP * 8;
         const int rl = allow_lds(llda_readout_theta_wide_kernel, lds);

@@ -73,7 +73,7 @@ def test_every_layout_and_vocabulary_size(K):
 def test_ties(K):
     rng = np.random.default_rng(100 + K)
     for V in (17, 300, 5000):
-        for n in (1, 10, 16):
+        for n in (1, 2, 4, 8, 10, 16):                                # every list size the kernels are built for, each filled
             check(rng.integers(0, 3, size=(K, V)), n)                 # {0, 1, 2}: ties in every list
     idx, cnt = run(np.zeros((K, 700), dtype=np.int64), 16)
     assert np.array_equal(idx, np.tile(np.arange(16, dtype=np.int32), (K, 1))) and (cnt == 0).all()
