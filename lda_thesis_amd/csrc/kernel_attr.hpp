@@ -37,6 +37,7 @@ struct AttrParams : DocModel {
 
 constexpr int ATTR_WAVES = 4;                           // wavefronts of a workgroup (wave and group kernels)
 constexpr int ATTR_MAX_TOP = 4;
+constexpr int64_t ATTR_LDS_MAX_BLOCKS = 1 << 16;        // workgroups of llda_attr_lds_kernel at most: each takes its documents in turn
 constexpr int attr_u(int NI) { return NI <= 2 ? 4 : NI <= 8 ? 2 : 1; }     // sites in flight in the wave kernel: NI = 1, 2 | 4, 8 | 16
 
 __device__ __forceinline__ bool attr_good(double p)

@@ -429,6 +429,7 @@ struct SetsParams {
 };
 
 constexpr int SETS_WAVES = 4;
+constexpr int SETS_MAX_BLOCKS = 1024;                     // workgroups at most: each takes its rounds of SETS_WAVES documents in turn
 
 __global__ void __launch_bounds__(SETS_WAVES * 64) llda_label_sets_kernel(const SetsParams P)
 {

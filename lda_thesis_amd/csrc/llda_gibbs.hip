@@ -454,7 +454,7 @@ int launch_attr(const AttrParams &P, hipStream_t st)
             const size_t lds = (size_t)2 * P.K * sizeof(double);                 // theta and credit: at most 123 008 bytes
             const int rl = allow_lds(llda_attr_lds_kernel<SITES>, lds);
             if (rl) return rl;
-            hipLaunchKernelGGL(llda_attr_lds_kernel<SITES>, doc_grid(P.D, 1 << 16), dim3(64), lds, st, P);
+            hipLaunchKernelGGL(llda_attr_lds_kernel<SITES>, doc_grid(P.D, ATTR_LDS_MAX_BLOCKS), dim3(64), lds, st, P);
             return launched();
         });
 }
@@ -1239,7 +1239,7 @@ int llda_label_sets(const llda_sets_args *a, void *stream)
     if (rl) return rl;
     const int64_t rounds = (a->D + SETS_WAVES - 1) / SETS_WAVES;
     // every workgroup flushes K counters: a few workgroups per compute unit, each with many documents
-    hipLaunchKernelGGL(llda_label_sets_kernel, dim3((unsigned)(rounds < 1024 ? rounds : 1024)), dim3(SETS_WAVES * 64), lds, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(llda_label_sets_kernel, dim3((unsigned)(rounds < SETS_MAX_BLOCKS ? rounds : SETS_MAX_BLOCKS)), dim3(SETS_WAVES * 64), lds, (hipStream_t)stream, P);
     return launched();
 }
 
