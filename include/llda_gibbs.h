@@ -207,8 +207,11 @@ typedef struct llda_sweep_args {
                                     walks a document with K / 32 lanes x 32 slots (kernel_quad.hpp), FOUR documents per wavefront at
                                     K = 512, eight at 256, sixteen at 128 -- the per-iteration work of scan, search, pick and count
                                     update is shared by that many sites.  A site whose row is not flagged
-                                    reads the int32 row (no prefetch: meant to be rare).  Bit 31 of csc_pos is ignored.  Results do
-                                    not depend on it. */
+                                    reads the int32 row (no prefetch: meant to be rare).  Bit 31 of csc_pos is ignored.  The kernel
+                                    forms 32-bit byte offsets into n_kw16 and into the commit log: V < 2^22 (LLDA_E_BAD_ARG
+                                    otherwise), and every csc_pos below 2^30 -- a bound on the sites of the whole LOG, which a shard
+                                    cut into several calls shares; llda_sweep sees one call's n_sites and cannot check it.  Results
+                                    do not depend on it. */
     const int32_t *img_col;      /* [dev] [KP] optional (ABI 20), with n_kw_img: the image column that holds the count of every device
                                     position -- the inverse of the col_src handed to llda_pack_image_cols.  The sparse-label kernel is
                                     bound by the L2's line fills: an image whose columns are ordered so that topics which are allowed

@@ -59,7 +59,7 @@ class GibbsSampler(object):
                (reference ``labs``), or a CSR pair (lab_off, lab_idx) of allowed topic ids.
     counts   : None -> counts are built on the device from z (LabeledLDA.py:89-92) and, when
                sharded, all-reduced; or a dict(n_d_k=(D,K), n_k_v=(K,V), n_zk=(K,)) in reference
-               layout for the LOCAL documents / GLOBAL matrices (keeps e.g. SubLDA's phantom columns).
+               layout for the LOCAL documents / GLOBAL matrices (keeps e.g. SubLDA's phantom columns); numpy or torch.
     seed, stream_id, doc_base : RNG key / counter words (doc_base = global id of local doc 0).
     group    : torch.distributed process group (None = default group when initialised).
     sparse_labels : True (default) = documents that allow few topics run through the sparse kernel when it
@@ -238,7 +238,8 @@ class GibbsSampler(object):
                 dist.all_reduce(self._counts, group=self.group)
         else:
             self.n_dk[:, self._topic_pos] = self._as_dev(counts["n_d_k"], torch.int32)
-            self.n_kw[:, self._topic_pos] = self._as_dev(np.asarray(counts["n_k_v"]).T, torch.int32)
+            n_k_v = counts["n_k_v"]                       # (a device tensor stays on the device: a vocabulary of millions)
+            self.n_kw[:, self._topic_pos] = self._as_dev(n_k_v.t() if isinstance(n_k_v, torch.Tensor) else np.asarray(n_k_v).T, torch.int32)
             self.n_k[self._topic_pos] = self._as_dev(counts["n_zk"], torch.int32)
 
     def _make_scratch(self):

@@ -128,7 +128,9 @@ def rows(rows16, quad, S, V, KP, rows16_ok, quad_ok, max_doc_tokens, tokens_max,
     four_waves = 0 < tokens < 65536       # the kernels pack n_dk with its sweep-start value and run four waves per SIMD
     if auto and not four_waves and V * KP * 4 < min_bytes:
         return keep
-    # (the quad kernel addresses the image and the commit log with 32-bit byte offsets)
+    # (the quad kernel addresses the image and the commit log with 32-bit byte offsets.  S is the whole shard, not a call: the calls
+    # of a shard share one log, and csrc/sweep_plan.hpp sees one call's n_sites only -- a shard of 2^30 sites and more sweeps with the
+    # two-document kernel, tests/test_gpu_offset_edges.py two_calls)
     as_quad = bool(quad is not False and four_waves and quad_ok and V < (1 << 22) and S < (1 << 30))
     if as_quad and quad is None and too_many_wide_sites(wide_share(), S, max_wide_sites):
         as_quad = False                   # ... the two-document kernel's prefetched int32 rows

@@ -184,10 +184,11 @@ int llda_oracle_draw(int K, const double *prob, double u)
 
 /* ---------------- one document ----------------
  * n_zk_work: the n_zk this document sees (mutated in place; caller decides what it starts as)
+ * ld:        row length of n_k_v (V for the whole matrix; V itself only enters V * beta)
  * col_adj:   snapshot mode -> the n_k_v column is read from the sweep-start matrix and only the
  *            site's own -f at z_old is applied (word ids are unique inside a document);
  *            sequential mode -> n_k_v is mutated in place like the reference does. */
-static int do_doc(const layout_t *L, int snapshot, int64_t d, int K, int64_t V,
+static int do_doc(const layout_t *L, int snapshot, int64_t d, int K, int64_t V, int64_t ld,
                   const int64_t *doc_off, const int32_t *word, const int32_t *freq, int32_t *z,
                   const uint8_t *labs, int64_t *n_d_k, int64_t *n_k_v, int64_t *n_zk_work,
                   double alpha, double beta, uint64_t seed, uint32_t sweep, uint32_t stream,
@@ -200,11 +201,11 @@ static int do_doc(const layout_t *L, int snapshot, int64_t d, int K, int64_t V,
         const int64_t v = word[i];
         const int64_t f = freq[i];
         const int zo = z[i];
-        if (!snapshot) n_k_v[(int64_t)zo * V + v] -= f;
+        if (!snapshot) n_k_v[(int64_t)zo * ld + v] -= f;
         row[zo] -= f;
         n_zk_work[zo] -= f;
         for (int k = 0; k < K; k++) {
-            int64_t nkv = n_k_v[(int64_t)k * V + v];
+            int64_t nkv = n_k_v[(int64_t)k * ld + v];
             if (snapshot && k == zo) nkv -= f;
             double a = (double)row[k] + alpha;
             double num_b = (double)nkv + beta;
@@ -217,7 +218,7 @@ static int do_doc(const layout_t *L, int snapshot, int64_t d, int K, int64_t V,
         int zn = draw_keyed(L, prob, u);
         if (zn < 0) return -3;
         z[i] = zn;
-        if (!snapshot) n_k_v[(int64_t)zn * V + v] += f;
+        if (!snapshot) n_k_v[(int64_t)zn * ld + v] += f;
         row[zn] += f;
         n_zk_work[zn] += f;
     }
@@ -237,7 +238,7 @@ int llda_oracle_sweep(int mode, int64_t D, int K, int64_t V,
     if (mode == 0) {
         double prob[MAX_KP];
         for (int64_t d = 0; d < D; d++) {
-            int rc = do_doc(&L, 0, d, K, V, doc_off, word, freq, z, labs, n_d_k, n_k_v, n_zk,
+            int rc = do_doc(&L, 0, d, K, V, V, doc_off, word, freq, z, labs, n_d_k, n_k_v, n_zk,
                             alpha, beta, seed, sweep, stream, doc_base, prob);
             if (rc) return rc;
         }
@@ -256,7 +257,7 @@ int llda_oracle_sweep(int mode, int64_t D, int K, int64_t V,
 #pragma omp for schedule(dynamic, 16)
         for (int64_t d = 0; d < D; d++) {
             memcpy(work, n_zk, sizeof(int64_t) * (size_t)K);
-            int rc = do_doc(&L, 1, d, K, V, doc_off, word, freq, z, labs, n_d_k, n_k_v, work,
+            int rc = do_doc(&L, 1, d, K, V, V, doc_off, word, freq, z, labs, n_d_k, n_k_v, work,
                             alpha, beta, seed, sweep, stream, doc_base, prob);
             if (rc) {
 #pragma omp atomic write
@@ -282,14 +283,18 @@ int llda_oracle_sweep(int mode, int64_t D, int K, int64_t V,
  * n_sel documents picked at random can be checked without sweeping the rest: local document d (CSR doc_off /
  * word / freq / z, rows labs[d] and n_d_k[d]) has the global id doc_ids[d] for the RNG key.  z and n_d_k are
  * updated; n_k_v and n_zk are the sweep-start counts and are NOT modified (the deltas of the other documents
- * are not known here).  labs == NULL: every topic allowed. */
+ * are not known here).  labs == NULL: every topic allowed.
+ * row_len (0: V): the length of a row of n_k_v.  A caller that holds the columns of the selection's words only renumbers the words
+ * 0 .. row_len - 1 and passes the true V, which then enters nothing but V * beta: no (K, V) matrix for a vocabulary of millions. */
 int llda_oracle_sweep_docs(int64_t n_sel, const int64_t *doc_ids, int K, int64_t V,
                            const int64_t *doc_off, const int32_t *word, const int32_t *freq, int32_t *z,
                            const uint8_t *labs, int64_t *n_d_k, const int64_t *n_k_v, const int64_t *n_zk,
-                           double alpha, double beta, uint64_t seed, uint32_t sweep, uint32_t stream, int threads)
+                           double alpha, double beta, uint64_t seed, uint32_t sweep, uint32_t stream, int threads,
+                           int64_t row_len)
 {
     layout_t L;
     if (make_layout(&L, K)) return -1;
+    if (row_len <= 0) row_len = V;
     uint8_t *ones = NULL;
     if (!labs) {
         ones = (uint8_t *)malloc((size_t)K);
@@ -307,7 +312,7 @@ int llda_oracle_sweep_docs(int64_t n_sel, const int64_t *doc_ids, int K, int64_t
             memcpy(work, n_zk, sizeof(int64_t) * (size_t)K);
             /* do_doc indexes labs by d: hand it a base that makes row d the all-ones row when labs is absent */
             const uint8_t *lab_base = labs ? labs : ones - d * K;
-            int rc = do_doc(&L, 1, d, K, V, doc_off, word, freq, z, lab_base, n_d_k, (int64_t *)n_k_v, work,
+            int rc = do_doc(&L, 1, d, K, V, row_len, doc_off, word, freq, z, lab_base, n_d_k, (int64_t *)n_k_v, work,
                             alpha, beta, seed, sweep, stream, doc_ids[d] - d, prob);
             if (rc) {
 #pragma omp atomic write
