@@ -36,6 +36,7 @@ from fractions import Fraction
 
 import numpy as np
 
+import layoutclasses
 import llda_oracle as orc
 from neartie import _gap, _site_scores
 
@@ -534,6 +535,9 @@ GENERAL = [(K, dense) for K in (9, 40, 130, 257, 777, 968, 1024) for dense in (T
 QUAD = [512, 256, 128, 100, 400]
 SPARSE = [(40, 7, 0), (392, 7, 0), (512, 7, 8), (512, 20, 16), (777, 40, 0), (1031, 7, 0), (2048, 7, 8)]        # (K, labels, image)
 WIDE = [(1031, False), (2048, True), (3000, False)]
+# the largest K of five and of seven tiers (tests/layoutclasses.py): the scan's carry runs over more than four tiers, the last tier is full
+# (both with general masks: exact_signed_gap walks the allowed topics in Python integers, and a dense state of 4 295 topics takes 26 s)
+WIDE += [(layoutclasses.tier_ks()[5][1], False), (layoutclasses.tier_ks()[7][1], False)]
 BATCH = [(5, 4, 5), (60, 9, 15), (128, 17, 32), (100, 33, 64)]                                                    # (K, fewest, most allowed topics)
 
 

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import foldinref
+import layoutclasses
 from countref import Guarded
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +29,8 @@ V = 60                                         # word V - 1 loads on no topic
 STREAM = 0x80C0FFEE
 C_INIT = 1.0005
 GRID_KS = [1, 2, 8, 9, 16, 17, 33, 60, 96, 129, 257, 512, 777, 968, 969, 1031, 2100]      # 968: last narrow, 969: first wide
+# five tiers with one leaf in the last (the smallest such K) and seven full tiers with a 7-topic tail (the largest): tests/layoutclasses.py
+GRID_KS += [layoutclasses.tier_ks()[5][0], layoutclasses.tier_ks()[7][1]]
 SINGLE_KS = [40, 512, 1031]
 SETTINGS = {       # LabeledLDA.run_test; CascadeLDA's flat run_test with cascade_test's fall-back switched on
     "llda": dict(alpha=0.1, beta=0.0, c_loop=1.0000005, beta_fallback=False, avg_mode=0),

@@ -4,6 +4,7 @@ Bit-exact for every integer array after every sweep."""
 import numpy as np
 import pytest
 
+import layoutclasses
 from conftest import golden_names, load_golden
 from helpers import assert_state_equal, c_state
 
@@ -243,20 +244,29 @@ def synth(rng, D, V, K, n_lo, n_hi, dense, fmax=3):
     return doc_off, word, freq, labs, z
 
 
-@pytest.mark.parametrize("K,dense,D,V", [(7, True, 300, 200), (64, True, 400, 500), (128, True, 300, 1000),
-                                         (392, False, 300, 800), (512, True, 96, 2000), (1024, True, 40, 600),
-                                         (300, True, 64, 500), (100, False, 1000, 300),
-                                         # every (lanes per document, slots per lane, tail) shape of the layout
-                                         (3, True, 200, 100), (15, False, 200, 150), (17, True, 150, 200),
-                                         (33, True, 150, 200), (60, True, 120, 300), (90, True, 120, 300),
-                                         (96, True, 100, 300), (129, True, 100, 300), (190, False, 100, 400),
-                                         (256, True, 80, 400), (257, True, 80, 400), (640, True, 50, 500),
-                                         (777, True, 40, 500), (900, True, 40, 500), (968, True, 32, 500),
-                                         # wide layouts: more than 8 pairwise leaves, 2 .. 8 tiers of 64 lanes (the last
-                                         # three need more than 64 KB of LDS per wavefront)
-                                         (969, True, 32, 500), (1500, False, 40, 400), (2047, True, 24, 300),
-                                         (4096, True, 16, 300), (5000, False, 24, 300), (6000, True, 12, 200),
-                                         (7688, True, 12, 200)])
+SEEDED = [(7, True, 300, 200), (64, True, 400, 500), (128, True, 300, 1000),
+          (392, False, 300, 800), (512, True, 96, 2000), (1024, True, 40, 600),
+          (300, True, 64, 500), (100, False, 1000, 300),
+          # every (lanes per document, slots per lane, tail) shape of the layout
+          (3, True, 200, 100), (15, False, 200, 150), (17, True, 150, 200),
+          (33, True, 150, 200), (60, True, 120, 300), (90, True, 120, 300),
+          (96, True, 100, 300), (129, True, 100, 300), (190, False, 100, 400),
+          (256, True, 80, 400), (257, True, 80, 400), (640, True, 50, 500),
+          (777, True, 40, 500), (900, True, 40, 500), (968, True, 32, 500),
+          # wide layouts: more than 8 pairwise leaves, 2 .. 8 tiers of 64 lanes (the last
+          # three need more than 64 KB of LDS per wavefront)
+          (969, True, 32, 500), (1500, False, 40, 400), (2047, True, 24, 300),
+          (4096, True, 16, 300), (5000, False, 24, 300), (6000, True, 12, 200),
+          (7688, True, 12, 200)]
+# the seams of the narrow classes: the smallest and the largest K of every (lanes per document, slots per lane) not in the list above
+# (the classes overlap -- 185 and 249 open the 16-slot classes below the ends of the 12-slot ones: tests/layoutclasses.py)
+SEEDED += [(K, i % 2 == 0, 60 if K <= 256 else 40, 300 if K <= 256 else 400)
+           for i, K in enumerate(layoutclasses.seam_ks(have=[c[0] for c in SEEDED]))]
+# five, six and seven tiers: the smallest K of each (the last tier holds one leaf)
+SEEDED += [(K, i % 2 == 1, 12, 200) for i, K in enumerate(layoutclasses.new_tier_ks())]
+
+
+@pytest.mark.parametrize("K,dense,D,V", SEEDED)
 def test_seeded_inputs_vs_c_oracle(c_oracle, K, dense, D, V):
     """larger seeded inputs: HIP == C oracle (snapshot mode) after 3 sweeps, every integer."""
     from lda_thesis_amd.sampler import GibbsSampler
@@ -749,13 +759,14 @@ def test_sparse_kernel_matches_reference_o3(name, margin, image):
 
 @pytest.mark.parametrize("margin", [-1, 6])
 @pytest.mark.parametrize("K", [9, 40, 100, 129, 190, 257, 392, 640, 777, 900, 968, 1024,
-                               1031, 1500, 2100, 3000, 7688])      # the last five: wide layouts (wide exact tier, LDS lock)
+                               1031, 1500, 2100, 3000, 7688]       # the last five: wide layouts (wide exact tier, LDS lock)
+                         + layoutclasses.new_tier_ks())            # ... and the smallest K of five, six and seven tiers
 def test_sparse_kernel_exact_tier_on_every_layout_shape(c_oracle, K, margin):
     _sparse_exact_tier_case(c_oracle, K, margin, 0)
 
 
-@pytest.mark.parametrize("image", [8, 16])
-@pytest.mark.parametrize("K", [9, 129, 392, 777, 1024, 1031, 3000])
+@pytest.mark.parametrize("K,image", [(K, image) for image in (8, 16) for K in (9, 129, 392, 777, 1024, 1031, 3000)]
+                         + [(layoutclasses.new_tier_ks()[0], 8)])  # (five tiers: the 8-bit image only)
 def test_sparse_kernel_exact_tier_with_the_narrow_image(c_oracle, K, image):
     """the same with the gathers going through the 8- / 16-bit image: the exact tier sees the escaped counts too"""
     _sparse_exact_tier_case(c_oracle, K, 6, image)

@@ -11,6 +11,7 @@ padding into the row sum); n_kw, n_k and den carry poison in the padding, which 
 import numpy as np
 import pytest
 
+import layoutclasses
 import readoutref as rr
 from countref import Guarded
 
@@ -376,7 +377,8 @@ def test_phi_on_a_side_stream():
 # llda_loglik, wide layouts, per document
 # ------------------------------------------------------------------------------------------------
 U = 2.0 ** -53
-LOGLIK_WIDE_KS = [969, 5000, 7688]
+LOGLIK_WIDE_KS = [969, 5000, 7688] + layoutclasses.new_tier_ks("largest")   # ... and five, six and seven FULL tiers with a 7-topic tail
+GEOMETRY.update({K: (64 * nt, 16, 7, True) for nt, K in zip((5, 6, 7), layoutclasses.new_tier_ks("largest"))})
 
 
 def check_loglik_per_document(K, masks, **case):

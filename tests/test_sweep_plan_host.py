@@ -11,11 +11,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import layoutclasses
 from conftest import ROOT
 
 OK, BAD_K, BAD_ARG = 0, -1, -2
 FAMILIES = ("none", "exact", "tiered", "rows16", "quad", "sparse", "wide_sparse", "wide_f32", "wide_reg", "wide_lds")
-KS = (8, 100, 128, 256, 392, 512, 1024, 1031, 2048, 3000, 7688)
+NEW_TIER_KS = tuple(layoutclasses.new_tier_ks())                  # the smallest K of five, six and seven tiers
+KS = (8, 100, 128, 256, 392, 512, 1024, 1031, 2048, 3000, 7688) + NEW_TIER_KS
 DMS = tuple(range(-20, 21))
 MARGIN0, MARGIN0_WIDE, MARGIN0_QUAD = 2.0 ** -17, 112 * 2.0 ** -24, 104 * 2.0 ** -24      # the production build's
 f32 = lambda x: float(np.float32(x))
@@ -273,7 +275,7 @@ def test_plan_over_the_grid(run_plans):
     lay = {K: layout(K) for K in KS}
     assert {L["G"] for L in lay.values() if not L["wide"]} == {8, 16, 32, 64}
     tiers = {L["tiers"] for L in lay.values() if L["wide"]}
-    assert {2, 8} <= tiers and tiers & {3, 4}
+    assert {2, 8} <= tiers and tiers & {3, 4} and {5, 6, 7} <= tiers
     cases = [(lay[K], args(dm=dm, **s)) for s in scenarios() for K in KS for dm in DMS]
     got = run_plans(cases)
     check(cases, got)
@@ -306,6 +308,38 @@ def test_every_kernel_hook_selects_its_own_plan(run_plans):
     # QUAD_HOOKS_OUT: production runs the instantiation without the hooks only when the build compiled them out
     q = run_plans([(L512, args(dm=0, hooks_out=h, **quad)) for h in (1, 0)])
     assert [g["hooks"] for g in q] == [0, 1]
+
+
+def test_five_six_and_seven_tiers_take_every_wide_form(run_plans):
+    """the widths whose dynamic LDS crosses the 64 KB opt-in at new sizes: every debug_margin, with and without scratch, a corpus
+    with and without a document of 2^15 tokens, tiny priors; slim only where -7 forces it"""
+    P = 4096
+    lays = [layout(K) for K in NEW_TIER_KS]
+    assert [(L["tiers"], L["T"], L["KP"]) for L in lays] == [(5, 16, 5120), (6, 16, 6144), (7, 16, 7168)]
+    kinds = dict(light=dict(max_doc_tokens=32767, scratch=P, scratch_bytes=1 << 30), no_scratch=dict(max_doc_tokens=32767),
+                 heavy=dict(max_doc_tokens=32768, scratch=P, scratch_bytes=1 << 30), unknown=dict(scratch=P, scratch_bytes=1 << 30),
+                 tiny=dict(max_doc_tokens=32767, scratch=P, scratch_bytes=1 << 30, alpha=1e-9, beta=1e-9))
+    cases = [(L, args(dm=dm, dense_mask=mask, **kw)) for L in lays for kw in kinds.values() for mask in (0, 1) for dm in DMS]
+    got = run_plans(cases)
+    check(cases, got)
+    fat, full = {5: 51200, 6: 61440, 7: 71680}, {5: 81920, 6: 98304, 7: 114688}
+    seen = set()
+    for (L, a), g in zip(cases, got):
+        assert g["rc"] == OK and g["nt"] == L["tiers"] and g["block"] == 64, (L["K"], a["dm"])
+        fam, dm, nt = FAMILIES[g["family"]], a["dm"], L["tiers"]
+        light = a["max_doc_tokens"] == 32767
+        if a["alpha"] < 1e-6:
+            assert (fam, g["tiered"], g["lds"]) == ("wide_lds", 0, full[nt])
+        elif dm == -3:
+            assert (fam, g["tiered"], g["lds"]) == ("wide_lds", 1, full[nt])
+        elif light and (dm >= -1 or dm in (-6, -7)):
+            slim = dm == -7 and bool(a["scratch"])
+            assert (fam, g["tc"], g["slim"]) == ("wide_f32", 4, int(slim)) and g["lds"] == (L["KP"] * 6 if slim else fat[nt])
+        else:
+            compact = light and dm != -4
+            assert (fam, g["compact"]) == ("wide_reg", int(compact)) and g["lds"] == (fat[nt] if compact else full[nt])
+        seen.add((nt, fam, g["slim"] if fam == "wide_f32" else g["compact"] if fam == "wide_reg" else g["tiered"]))
+    assert seen == {(nt, fam, v) for nt in (5, 6, 7) for fam in ("wide_f32", "wide_reg", "wide_lds") for v in (0, 1)}
 
 
 def test_refusals(run_plans):

@@ -25,6 +25,9 @@ model disagrees with the C oracle -- measurements; the tests ask for one each:
   wide    2048 dense   48  48    25  11   7   2  28   5.8      wide    3000 masked  48  48    20  16   8   5  24   2.7
   batched    5 (0)     48  48     9   0   4  18  31   4.3      batched   60 (1)     48  48    16   7   7   9  21   3.6
   batched  128 (2)     48  48    10   5   4  11  17   4.0      batched  100 (3)     48  48    14   5   4   9  24   3.2
+  wide    4167 masked  48  48    14  14   5   4  21   8.2      wide    4295 masked  48  48    22  11   7   9  25  12.9
+(4167 and 4295: the largest K of five and of seven tiers, tests/layoutclasses.py tier_ks().  Their seconds are from a slower machine,
+on which wide 3000 took 7.6 s: 1.1 and 1.7 times that state's.)
 (s: seconds to generate the state on one core of the development machine; sweepties.state is cached, so the host and the GPU tests of a
 process pay once.  numpy sums fewer than 8 terms sequentially: at K = 5 model (b) IS the pipeline and cannot be caught.  With fewer than
 some 48 ties a state missed a model now and then -- see sweepties.N_DOCS.)
