@@ -1,5 +1,6 @@
 // kernel_wide.hpp -- "wide" layouts: K with more than 8 pairwise leaves (some K in 969..1023, every K > 1024, up to
-// LLDA_MAX_K): llda_sweep_wide_reg_kernel / llda_sweep_wide_kernel, llda_loglik_wide_kernel,
+// LLDA_MAX_K): llda_sweep_wide_f32_kernel / llda_sweep_wide_reg_kernel / llda_sweep_wide_kernel (the fp64 decision,
+// wide_decide64, and the count state, WideCounts, shared by the first and the last), llda_loglik_wide_kernel,
 // llda_readout_theta_wide_kernel, llda_foldin_init_wide_kernel / llda_foldin_wide_kernel
 // Part of the single translation unit llda_gibbs.hip (included in order; see the contents list there).
 #pragma once
@@ -277,27 +278,36 @@ __device__ __forceinline__ void wide_factors(double *fac, const int *s_ndk, cons
     }
 }
 
-// the tier's decision for one site: position, or -1 when the margin cannot decide it
-__device__ __forceinline__ int wide_tier(const double *fac, const int4 *xrow, const WideLayout &W, double u, int zo, int f,
-                                         double beta, double margin_rel, int lane)
+// The fp64 two-pass decision of one site, shared by the LDS-only and the fp32 kernels: lane totals of
+// score = fac * (count + beta) in a first pass, the scan over the virtual lanes, then a second pass that recomputes each
+// prefix value and compares it with t -+ margin.  Returns the position, or -1 when the margin cannot decide the site (a
+// prefix value inside the band, a total that is not positive, no hit).  The association order of `run` and of wide_scan is
+// what the 2^-40 margin argument rests on: it is written here and, in the same statements, in
+// llda_sweep_wide_reg_kernel (see there why).
+//   count_at(t, c, j): the site's count at slot 4c + j of virtual lane 64t + lane, its own count already removed
+//   NT_STATIC:         the tiers when the kernel knows them (G = 64 * NT_STATIC), 0: tiers and G from W
+//   T:                 slots per virtual lane (8 / 12 / 16); a kernel with the row in registers has its chunk loops
+//                      unrolled (c < 4, guarded), one that reads the row from memory keeps them rolled
+template <int NT_STATIC, class CountAt>
+__device__ __forceinline__ int wide_decide64(const double *fac, CountAt count_at, const WideLayout &W, int T, double u,
+                                             double beta, double margin_rel, int lane)
 {
-    const int T = W.T, G = W.G, NT = W.NT, KP4 = W.KP >> 2;
+    const int NT = NT_STATIC ? NT_STATIC : W.NT, G = NT_STATIC ? 64 * NT_STATIC : W.G, KP4 = W.KP >> 2;
+    const int TC = T >> 2, TC_LOOP = NT_STATIC ? 4 : TC;
+    constexpr int UNROLL_C = NT_STATIC ? 4 : 1;
     double X[WIDE_MAX_TIERS];
 #pragma unroll
     for (int t = 0; t < WIDE_MAX_TIERS; ++t) {
         X[t] = 0.0;
         if (t < NT) {
-            const int gv = t * 64 + lane;
             double run = 0.0;
-            for (int c = 0; c < (T >> 2); ++c) {
-                const int q = c * G + gv;
-                const int4 x4 = xrow[q];
-                const double *p = fac + q;
-                const int xs[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll UNROLL_C
+            for (int c = 0; c < TC_LOOP; ++c)
+                if (c < TC) {
+                    const double *p = fac + (c * G + t * 64 + lane);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    run = run + p[j * KP4] * ((double)(xs[j] - ((((q << 2) | j) == zo) ? f : 0)) + beta);
-            }
+                    for (int j = 0; j < 4; ++j) run = run + p[j * KP4] * ((double)count_at(t, c, j) + beta);
+                }
             X[t] = run;
         }
     }
@@ -310,21 +320,19 @@ __device__ __forceinline__ int wide_tier(const double *fac, const int4 *xrow, co
         if (t < NT) {
             const double tg = tt - wide_prev(X[t], X[t > 0 ? t - 1 : 0], t > 0, lane);
             const double lo = tg - m, hi = tg + m;
-            const int gv = t * 64 + lane;
             double run = 0.0;
             uint32_t hm = 0, um = 0;
-            for (int c = 0; c < (T >> 2); ++c) {
-                const int q = c * G + gv;
-                const int4 x4 = xrow[q];
-                const double *p = fac + q;
-                const int xs[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll UNROLL_C
+            for (int c = 0; c < TC_LOOP; ++c)
+                if (c < TC) {
+                    const double *p = fac + (c * G + t * 64 + lane);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    run = run + p[j * KP4] * ((double)(xs[j] - ((((q << 2) | j) == zo) ? f : 0)) + beta);
-                    hm |= (run > hi ? 1u : 0u) << (4 * c + j);
-                    um |= ((run > lo && !(run > hi)) ? 1u : 0u) << (4 * c + j);
+                    for (int j = 0; j < 4; ++j) {
+                        run = run + p[j * KP4] * ((double)count_at(t, c, j) + beta);
+                        hm |= (run > hi ? 1u : 0u) << (4 * c + j);
+                        um |= ((run > lo && !(run > hi)) ? 1u : 0u) << (4 * c + j);
+                    }
                 }
-            }
             const uint64_t bh = __ballot(hm != 0);
             unsure = unsure || __ballot(um != 0) != 0;
             if (hit < 0 && bh != 0) {
@@ -335,6 +343,19 @@ __device__ __forceinline__ int wide_tier(const double *fac, const int4 *xrow, co
         }
     }
     return unsure ? -1 : hit;
+}
+
+// the decision with the counts read from the row in memory (LDS-only kernel, rare tiers of the SLIM kernel)
+__device__ __forceinline__ int wide_tier(const double *fac, const int4 *xrow, const WideLayout &W, double u, int zo, int f,
+                                         double beta, double margin_rel, int lane)
+{
+    const auto count_at = [&](int t, int c, int j) {
+        const int q = c * W.G + t * 64 + lane;
+        const int4 x4 = xrow[q];
+        const int xs[4] = {x4.x, x4.y, x4.z, x4.w};
+        return xs[j] - ((((q << 2) | j) == zo) ? f : 0);
+    };
+    return wide_decide64<0>(fac, count_at, W, W.T, u, beta, margin_rel, lane);
 }
 
 // one site through the reference's fp64 pipeline (LabeledLDA.py:113-119): scores into wv, np.sum, prob /= sum, keyed draw
@@ -374,6 +395,132 @@ __device__ inline int wide_exact_site(double *wv, const int *s_ndk, const int *s
     return zn;
 }
 
+// The topic counts of the document a wavefront samples -- its n_dk row and the n_k it sees -- in one of two forms:
+//   LDS copies (!COMPACT): both rows as int32 in LDS, position order, 8 bytes per position;
+//   COMPACT (the caller vouches that no document holds 32 768 tokens or more, llda_sweep_args.max_doc_tokens): the start
+//   values stay in HBM (the document's n_dk row, n_k: both constant while the document is sampled) and LDS holds ONE int16
+//   change per position (a topic of the document changes n_dk and the n_k it sees by the same amount).
+// `lds` is the wavefront's LDS behind its cached factors.  Lane 0 applies the two +-f of a site.
+template <bool COMPACT>
+struct WideCounts {
+    int *s_ndk, *s_nkc;                                          // (!COMPACT)
+    int16_t *s_dk;                                               // (COMPACT)
+    int32_t *ndk_row;
+    const int32_t *n_k;
+    int KP4;
+
+    __device__ __forceinline__ WideCounts(void *lds, int32_t *ndk_row_, const int32_t *n_k_, int KP)
+        : s_ndk(static_cast<int *>(lds)), s_nkc(static_cast<int *>(lds) + KP), s_dk(static_cast<int16_t *>(lds)),
+          ndk_row(ndk_row_), n_k(n_k_), KP4(KP >> 2) {}
+
+    // head of a document: no change yet, or the two rows copied
+    __device__ __forceinline__ void begin(int lane) const
+    {
+        for (int q = lane; q < KP4; q += 64) {
+            if constexpr (COMPACT) {
+                reinterpret_cast<int2 *>(s_dk)[q] = make_int2(0, 0);
+            } else {
+                reinterpret_cast<int4 *>(s_ndk)[q] = reinterpret_cast<const int4 *>(ndk_row)[q];
+                reinterpret_cast<int4 *>(s_nkc)[q] = reinterpret_cast<const int4 *>(n_k)[q];
+            }
+        }
+    }
+    // where wide_factors / wide_exact_site read the counts: start values (HBM) + change (LDS), or the LDS copies
+    __device__ __forceinline__ const int *ndk() const { return COMPACT ? ndk_row : s_ndk; }
+    __device__ __forceinline__ const int *nk() const { return COMPACT ? n_k : s_nkc; }
+    __device__ __forceinline__ const int16_t *dk() const { return COMPACT ? s_dk : nullptr; }
+    // the count of a position changes by df: returns its new (n_dk, n_k).  COMPACT: given the position's start values
+    // (L2 hits, fetched with start() ahead of time where the position is known ahead of time)
+    __device__ __forceinline__ int2 start(int pos) const
+    {
+        static_assert(COMPACT, "the LDS copies have no start values");
+        return make_int2(ndk_row[pos], n_k[pos]);
+    }
+    __device__ __forceinline__ int2 change(int pos, int df, int2 st) const
+    {
+        static_assert(COMPACT, "the LDS copies take change(pos, df)");
+        const int dz = (int)s_dk[pos] + df;
+        s_dk[pos] = (int16_t)dz;
+        return make_int2(st.x + dz, st.y + dz);
+    }
+    __device__ __forceinline__ int2 change(int pos, int df) const
+    {
+        static_assert(!COMPACT, "the compact form takes change(pos, df, start values)");
+        const int nd = s_ndk[pos] + df, nk = s_nkc[pos] + df;
+        s_ndk[pos] = nd; s_nkc[pos] = nk;
+        return make_int2(nd, nk);
+    }
+    // tail of a document: its changes into n_k_delta and into its n_dk row
+    __device__ __forceinline__ void flush(int lane, int32_t *n_k_delta) const
+    {
+        for (int q = lane; q < KP4; q += 64) {
+            if constexpr (COMPACT) {
+                const int2 pk = reinterpret_cast<const int2 *>(s_dk)[q];
+                if (pk.x | pk.y) {
+                    const int dl[4] = {(int)(int16_t)(pk.x & 0xFFFF), pk.x >> 16, (int)(int16_t)(pk.y & 0xFFFF), pk.y >> 16};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (dl[j]) {
+                            atomicAdd(n_k_delta + ((q << 2) | j), dl[j]);
+                            ndk_row[(q << 2) | j] += dl[j];
+                        }
+                }
+            } else {
+                const int4 old = reinterpret_cast<const int4 *>(ndk_row)[q];
+                const int4 cur = reinterpret_cast<const int4 *>(s_ndk)[q];
+                const int dl[4] = {cur.x - old.x, cur.y - old.y, cur.z - old.z, cur.w - old.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (dl[j]) atomicAdd(n_k_delta + ((q << 2) | j), dl[j]);
+                reinterpret_cast<int4 *>(ndk_row)[q] = cur;
+            }
+        }
+    }
+};
+
+// the cached factor of a position whose counts became c = (n_dk, n_k) (lane 0).  A cached factor is 0 exactly where the
+// label mask is, so the old value tells whether the topic is allowed: no mask load per site (`allowed`: known without it)
+template <class fac_t>
+__device__ __forceinline__ void wide_refresh_factor(fac_t *fac, int pos, int KP4, int2 c, bool allowed, double alpha, double vbeta)
+{
+    fac_t *pf = fac + fac_index(pos, KP4);
+    *pf = (fac_t)wide_factor(c.x, c.y, allowed || *pf != (fac_t)0, alpha, vbeta);
+}
+
+// statistics of a tiered kernel, as the narrow kernels: sites tier 0 left open (the fp32 kernel's alone), sites of the exact pipeline
+__device__ __forceinline__ void wide_report_status(const KParams &K, int lane, int n_unsure, int n_exact)
+{
+    if (lane == 0 && K.status) {
+        if (n_unsure) atomicAdd(K.status + 1, n_unsure);
+        if (n_exact) {
+            atomicOr(K.status, 2);
+            atomicAdd(K.status + 2, n_exact);
+        }
+    }
+}
+
+// The site scalars that run ahead of the fp32 kernel (the register kernel has the same statements in its body): word,
+// frequency, old topic and commit-log position of the sites n (._c) and n + 1 (._1) are in registers at the top of site n.
+struct WideSitesAhead {
+    int v_c, f_c, zo_c, c_c, v_1, f_1, zo_1, c_1;
+
+    __device__ __forceinline__ WideSitesAhead(const KParams &K, int64_t s0, int len)
+    {
+        v_c = K.word[s0]; f_c = K.freq[s0]; zo_c = K.z[s0];
+        const int64_t i1 = s0 + (len > 1 ? 1 : 0);
+        v_1 = K.word[i1]; f_1 = K.freq[i1]; zo_1 = K.z[i1];
+        c_c = K.csc_pos ? K.csc_pos[s0] : 0; c_1 = K.csc_pos ? K.csc_pos[i1] : 0;           // (commit-log positions)
+    }
+    // at site n, once its scalars are taken: ._c becomes site n + 1, ._1 site n + 2 (the last site again beyond the end)
+    __device__ __forceinline__ void advance(const KParams &K, int64_t s0, int n, int len)
+    {
+        v_c = v_1; f_c = f_1; zo_c = zo_1; c_c = c_1;
+        const int64_t i2 = s0 + (n + 2 < len ? n + 2 : len - 1);
+        v_1 = K.word[i2]; f_1 = K.freq[i2]; zo_1 = K.z[i2];
+        if (K.csc_pos) c_1 = K.csc_pos[i2];
+    }
+};
+
 template <bool TIERED>
 __global__ void __launch_bounds__(64) llda_sweep_wide_kernel(const WParams P)
 {
@@ -382,7 +529,6 @@ __global__ void __launch_bounds__(64) llda_sweep_wide_kernel(const WParams P)
     const WideLayout &W = P.w;
     const int lane = threadIdx.x, KP = W.KP, G = W.G;
     double *wv = s_wide;
-    int *s_ndk = reinterpret_cast<int *>(wv + KP), *s_nkc = s_ndk + KP;
     int n_exact = 0;
 
     for (int64_t idx = blockIdx.x; idx < K.D; idx += gridDim.x) {
@@ -390,13 +536,10 @@ __global__ void __launch_bounds__(64) llda_sweep_wide_kernel(const WParams P)
         const int64_t s0 = K.doc_off[d];
         const int len = (int)(K.doc_off[d + 1] - s0);
         if (len <= 0) continue;
-        int32_t *ndk_row = K.n_dk + d * KP;
-        for (int q = lane; q < (KP >> 2); q += 64) {
-            reinterpret_cast<int4 *>(s_ndk)[q] = reinterpret_cast<const int4 *>(ndk_row)[q];
-            reinterpret_cast<int4 *>(s_nkc)[q] = reinterpret_cast<const int4 *>(K.n_k)[q];
-        }
+        const WideCounts<false> cnt(wv + KP, K.n_dk + d * KP, K.n_k, KP);
+        cnt.begin(lane);
         const uint16_t *mrow = K.lab_mask + d * G;
-        if (TIERED) wide_factors(wv, s_ndk, s_nkc, nullptr, mrow, W, K.alpha, K.vbeta, lane);
+        if (TIERED) wide_factors(wv, cnt.ndk(), cnt.nk(), nullptr, mrow, W, K.alpha, K.vbeta, lane);
         const uint32_t gdoc = (uint32_t)(d + K.doc_base);
         uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
 
@@ -405,10 +548,8 @@ __global__ void __launch_bounds__(64) llda_sweep_wide_kernel(const WParams P)
             const int v = K.word[i], f = K.freq[i], zo = K.z[i];
             const double u = site_uniform<64>(K, n, n == 0, gdoc, lane, r0, r1, r2, r3);
             if (lane == 0) {                                                 // remove the site (LabeledLDA.py:109-111)
-                const int nd = s_ndk[zo] - f, nk = s_nkc[zo] - f;
-                s_ndk[zo] = nd; s_nkc[zo] = nk;
-                if (TIERED) wv[fac_index(zo, KP >> 2)] = wide_factor(nd, nk, wv[fac_index(zo, KP >> 2)] != 0.0, K.alpha, K.vbeta);   // (a cached factor is 0 exactly
-                                                                                             // where the label mask is)
+                const int2 c = cnt.change(zo, -f);
+                if (TIERED) wide_refresh_factor(wv, zo, KP >> 2, c, false, K.alpha, K.vbeta);
             }
             const int4 *xrow = reinterpret_cast<const int4 *>(K.n_kw + (int64_t)v * KP);
             int zn = -1;
@@ -416,30 +557,18 @@ __global__ void __launch_bounds__(64) llda_sweep_wide_kernel(const WParams P)
             const bool exact = zn < 0;
             if (exact) {
                 ++n_exact;
-                zn = wide_exact_site(wv, s_ndk, s_nkc, nullptr, mrow, xrow, W, K, zo, f, u, lane);
+                zn = wide_exact_site(wv, cnt.ndk(), cnt.nk(), nullptr, mrow, xrow, W, K, zo, f, u, lane);
             }
             if (lane == 0) {                                                 // add the site back (LabeledLDA.py:121-125)
-                const int nd = s_ndk[zn] + f, nk = s_nkc[zn] + f;
-                s_ndk[zn] = nd; s_nkc[zn] = nk;
-                if (TIERED && !exact) wv[fac_index(zn, KP >> 2)] = wide_factor(nd, nk, true, K.alpha, K.vbeta);
+                const int2 c = cnt.change(zn, f);
+                if (TIERED && !exact) wide_refresh_factor(wv, zn, KP >> 2, c, true, K.alpha, K.vbeta);
                 commit_site(K, i, v, f, zo, zn, K.csc_pos ? K.csc_pos[i] : 0, KP);
             }
-            if (TIERED && exact) wide_factors(wv, s_ndk, s_nkc, nullptr, mrow, W, K.alpha, K.vbeta, lane);
+            if (TIERED && exact) wide_factors(wv, cnt.ndk(), cnt.nk(), nullptr, mrow, W, K.alpha, K.vbeta, lane);
         }
-        for (int q = lane; q < (KP >> 2); q += 64) {
-            const int4 old = reinterpret_cast<const int4 *>(ndk_row)[q];
-            const int4 cur = reinterpret_cast<const int4 *>(s_ndk)[q];
-            const int dl[4] = {cur.x - old.x, cur.y - old.y, cur.z - old.z, cur.w - old.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (dl[j]) atomicAdd(K.n_k_delta + ((q << 2) | j), dl[j]);
-            reinterpret_cast<int4 *>(ndk_row)[q] = cur;
-        }
+        cnt.flush(lane, K.n_k_delta);
     }
-    if (TIERED && n_exact && lane == 0 && K.status) {                        // statistics, as the narrow kernels
-        atomicOr(K.status, 2);
-        atomicAdd(K.status + 2, n_exact);
-    }
+    if (TIERED) wide_report_status(K, lane, 0, n_exact);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -450,12 +579,14 @@ __global__ void __launch_bounds__(64) llda_sweep_wide_kernel(const WParams P)
 // Measured (tools/abl_wide.py): K = 2 048 119 -> 217 M sites/s, K = 4 096 37 -> 64, K = 7 688 11 -> 16.  Also prefetching the
 // row of site n+1 into a second register set was tried and is NOT faster (2 tiers: 210, 8 tiers: 9 -- it spills).
 // ---------------------------------------------------------------------------------------------
-// COMPACT (the caller vouches that no document holds 32 768 tokens or more, llda_sweep_args.max_doc_tokens): the
-// document's counts are not copied to LDS at all -- they are the start values in HBM (its n_dk row, n_k: both constant
-// while the document is sampled) plus ONE int16 change per position in LDS (a topic of the document changes n_dk and the
-// n_k it sees by the same amount).  10 bytes of LDS per position instead of 16: 8 wavefronts per CU instead of 5 at K = 2 048,
-// 4 instead of 2 at K = 4 096, 2 instead of 1 at K = 7 688 -- and this path is bound by exactly that.  Lane 0 fetches the two
-// start values of the old topic one site ahead and those of the new topic after the draw (L2 hits).
+// COMPACT: the document's counts in the compact form of WideCounts, not copied to LDS at all.  10 bytes of LDS per position
+// instead of 16: 8 wavefronts per CU instead of 5 at K = 2 048, 4 instead of 2 at K = 4 096, 2 instead of 1 at K = 7 688 -- and this
+// path is bound by exactly that.  Lane 0 fetches the two start values of the old topic one site ahead and those of the new
+// topic after the draw.
+// This kernel spells the decision (wide_decide64), the count updates (WideCounts) and the scalars ahead (WideSitesAhead) out
+// in its own statements: on the shared ones <2, true> ran 1.3 - 1.7 % slower (the allocator places its ~120 spilled SGPRs
+// differently), and neither the decision nor the count updates alone brought it back (profiles/wide_refactor.md).  A change
+// to one of the three shared pieces is made here too.
 template <int NT, bool COMPACT>
 __global__ void __launch_bounds__(64) llda_sweep_wide_reg_kernel(const WParams P)
 {
@@ -727,7 +858,6 @@ llda_sweep_wide_f32_kernel(const WParams P, const float margin0_rel, double *scr
     typedef typename std::conditional<SLIM, float, double>::type fac_t;
     const int lane = threadIdx.x, KP = W.KP, KP4 = W.KP >> 2;
     fac_t *wv = reinterpret_cast<fac_t *>(s_wide);              // factor of position p at (p & 3) * KP4 + (p >> 2)
-    int16_t *s_dk = reinterpret_cast<int16_t *>(wv + KP);        // change of n_dk (= of the n_k the document sees), position order
     double *scr = SLIM ? scratch + (size_t)blockIdx.x * KP : nullptr;    // the rare tiers' row of doubles
     const float beta32 = (float)K.beta;
     int n_unsure = 0, n_exact = 0;
@@ -739,9 +869,10 @@ llda_sweep_wide_f32_kernel(const WParams P, const float margin0_rel, double *scr
         if (len <= 0) continue;
         int32_t *ndk_row = K.n_dk + d * KP;
         const uint16_t *mrow = K.lab_mask + d * G;
-        for (int q = lane; q < KP4; q += 64) reinterpret_cast<int2 *>(s_dk)[q] = make_int2(0, 0);
+        const WideCounts<true> cnt(wv + KP, ndk_row, K.n_k, KP);
+        cnt.begin(lane);
         if constexpr (SLIM) wide_factors32(wv, ndk_row, K.n_k, mrow, W, K.alpha, K.vbeta, lane);
-        else wide_factors(wv, ndk_row, K.n_k, s_dk, mrow, W, K.alpha, K.vbeta, lane);
+        else wide_factors(wv, ndk_row, K.n_k, cnt.dk(), mrow, W, K.alpha, K.vbeta, lane);
         uint32_t mk[NT];                                          // allowed slots of this lane's virtual lanes
 #pragma unroll
         for (int t = 0; t < NT; ++t) mk[t] = mrow[t * 64 + lane];
@@ -762,43 +893,31 @@ llda_sweep_wide_f32_kernel(const WParams P, const float margin0_rel, double *scr
                     x[t][4 * c] = r.x; x[t][4 * c + 1] = r.y; x[t][4 * c + 2] = r.z; x[t][4 * c + 3] = r.w;
                 }
         };
-        // scalars of the sites n (._c) and n + 1 (._1) are in registers at the top of site n; the row of site n too
-        int v_c = K.word[s0], f_c = K.freq[s0], zo_c = K.z[s0];
-        const int64_t i1 = s0 + (len > 1 ? 1 : 0);
-        int v_1 = K.word[i1], f_1 = K.freq[i1], zo_1 = K.z[i1];
-        int c_c = K.csc_pos ? K.csc_pos[s0] : 0, c_1 = K.csc_pos ? K.csc_pos[i1] : 0;       // (commit-log positions)
+        WideSitesAhead ahead(K, s0, len);                           // (the row of site n is in registers at its top too)
         // (two row buffers need 32 * NT registers: beyond two tiers the allocator keeps them in scratch memory, so there the
         // row of a site is loaded at its top and only the scalars run ahead)
         constexpr bool PREFETCH = NT <= 2 && !SLIM;
         v16i xa[NT], xb[PREFETCH ? NT : 1];
-        if constexpr (PREFETCH) load_row(__builtin_amdgcn_readfirstlane(v_c), xa);
-        // a topic count of the document changes by df (lane 0): the int16 change and the cached factor; nd0, nk0 = the
-        // start values of the position (HBM; fetched ahead of time where the position is known ahead of time)
-        auto count_change = [&](const int pos, const int df, const int nd0, const int nk0) {
-            const int dz = (int)s_dk[pos] + df;
-            s_dk[pos] = (int16_t)dz;
-            fac_t *pf = wv + fac_index(pos, KP4);
-            // (a cached factor is 0 exactly where the label mask is: no mask load per site)
-            *pf = (fac_t)wide_factor(nd0 + dz, nk0 + dz, *pf != (fac_t)0, K.alpha, K.vbeta);
+        if constexpr (PREFETCH) load_row(__builtin_amdgcn_readfirstlane(ahead.v_c), xa);
+        // a topic count of the document changes by df (lane 0): the int16 change and the cached factor; st = the start
+        // values of the position
+        auto count_change = [&](const int pos, const int df, const int2 st) {
+            wide_refresh_factor(wv, pos, KP4, cnt.change(pos, df, st), false, K.alpha, K.vbeta);
         };
-        if (lane == 0) count_change(zo_c, -f_c, ndk_row[zo_c], K.n_k[zo_c]);    // site 0 leaves its topic (LabeledLDA.py:109-111)
+        if (lane == 0) count_change(ahead.zo_c, -ahead.f_c, cnt.start(ahead.zo_c));    // site 0 leaves its topic (LabeledLDA.py:109-111)
 
         auto site = [&](const int n, v16i (&x)[NT], v16i (&xnext)[PREFETCH ? NT : 1]) {
             const int64_t i = s0 + n;
-            const int v = __builtin_amdgcn_readfirstlane(v_c), f = __builtin_amdgcn_readfirstlane(f_c),
-                      zo = __builtin_amdgcn_readfirstlane(zo_c), cpos = c_c;
+            const int v = __builtin_amdgcn_readfirstlane(ahead.v_c), f = __builtin_amdgcn_readfirstlane(ahead.f_c),
+                      zo = __builtin_amdgcn_readfirstlane(ahead.zo_c), cpos = ahead.c_c;
             uint32_t ra, rb;
             site_random_bits<64>(K, n, n == 0, gdoc, lane, r0, r1, r2, r3, ra, rb);
             // row of site n + 1, scalars of site n + 2, start counts of site n + 1's old topic (needed at the end of this site)
-            if constexpr (PREFETCH) load_row(__builtin_amdgcn_readfirstlane(v_1), xnext);
+            if constexpr (PREFETCH) load_row(__builtin_amdgcn_readfirstlane(ahead.v_1), xnext);
             else load_row(v, x);
-            v_c = v_1; f_c = f_1; zo_c = zo_1; c_c = c_1;
-            const int nd0_n = ndk_row[zo_c], nk0_n = K.n_k[zo_c];
-            {
-                const int64_t i2 = s0 + (n + 2 < len ? n + 2 : len - 1);
-                v_1 = K.word[i2]; f_1 = K.freq[i2]; zo_1 = K.z[i2];
-                if (K.csc_pos) c_1 = K.csc_pos[i2];
-            }
+            const int2 st_n = cnt.start(ahead.zo_1);                // (BEFORE the loads of site n + 2: behind them the two-tier forms
+                                                                    // measured 1.3 - 2 % slower, profiles/wide_refactor.md)
+            ahead.advance(K, s0, n, len);
             // own count out of the row: position zo is slot 4 * chunk + (zo & 3) of virtual lane (zo >> 2) % G -- all uniform,
             // so it is ONE indexed register write in the lane that owns it
             {
@@ -868,81 +987,40 @@ llda_sweep_wide_f32_kernel(const WParams P, const float margin0_rel, double *scr
               ++n_unsure;
               if constexpr (SLIM) {
                 int ex = 0;
-                zn = wide_rare_tiers((const WParams *)__builtin_amdgcn_kernarg_segment_ptr(), scr, ndk_row, s_dk, mrow, v, zo, f, ra, rb,
-                                     lane, &ex);
+                zn = wide_rare_tiers((const WParams *)__builtin_amdgcn_kernarg_segment_ptr(), scr, ndk_row, cnt.dk(), mrow, v, zo, f, ra,
+                                     rb, lane, &ex);
                 n_exact += ex;
               } else {
                 // ---- tier 1: the fp64 two-pass decision of the register kernel on the same row and factors ----
                 const double u = uniform53(ra, rb);
-                double X[WIDE_MAX_TIERS];
-#pragma unroll
-                for (int t = 0; t < WIDE_MAX_TIERS; ++t) X[t] = 0.0;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    double run = 0.0;
-#pragma unroll
-                    for (int c = 0; c < TC; ++c) {
-                        const double *p = wv + (c * G + t * 64 + lane);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) run = run + p[j * KP4] * ((double)x[t][4 * c + j] + K.beta);
-                    }
-                    X[t] = run;
-                }
-                const double tot = wide_scan(X, NT, lane);
-                const double tt = u * tot, m = K.margin_rel * tot;
-                zn = -1;
-                bool unsure = !(tot > 0.0);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const double tg = tt - wide_prev(X[t], X[t > 0 ? t - 1 : 0], t > 0, lane);
-                    const double lo = tg - m, hi = tg + m;
-                    double run = 0.0;
-                    uint32_t hm = 0, um = 0;
-#pragma unroll
-                    for (int c = 0; c < TC; ++c) {
-                        const double *p = wv + (c * G + t * 64 + lane);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            run = run + p[j * KP4] * ((double)x[t][4 * c + j] + K.beta);
-                            hm |= (run > hi ? 1u : 0u) << (4 * c + j);
-                            um |= ((run > lo && !(run > hi)) ? 1u : 0u) << (4 * c + j);
-                        }
-                    }
-                    const uint64_t bh = __ballot(hm != 0);
-                    unsure = unsure || __ballot(um != 0) != 0;
-                    if (zn < 0 && bh != 0) {
-                        const int sl = (int)__ffsll((unsigned long long)bh) - 1;
-                        const int ss = __shfl((int)__ffs((int)(hm | 0x10000u)) - 1, sl, 64);
-                        zn = pos_of_rt(G, T, t * 64 + sl, ss);
-                    }
-                }
-                exact = unsure || zn < 0;
+                zn = wide_decide64<NT>(wv, [&](int t, int c, int j) { return x[t][4 * c + j]; }, W, T, u, K.beta, K.margin_rel, lane);
+                exact = zn < 0;
                 if (__builtin_expect(exact, 0)) {
                     ++n_exact;
                     // (the parameters through the kernel-argument segment: wide_sum indexes the layout's tables dynamically,
                     // and on the by-value copy that would put ALL of P into scratch memory -- and every pointer of the hot
                     // loop behind a scratch load)
                     const WParams *Pk = (const WParams *)__builtin_amdgcn_kernarg_segment_ptr();
-                    zn = wide_exact_site(wv, ndk_row, Pk->k.n_k, s_dk, mrow,
+                    zn = wide_exact_site(wv, ndk_row, Pk->k.n_k, cnt.dk(), mrow,
                                          reinterpret_cast<const int4 *>(Pk->k.n_kw + (int64_t)v * KP), Pk->w, Pk->k, zo, f, u, lane);
-                    wide_factors(wv, ndk_row, Pk->k.n_k, s_dk, mrow, Pk->w, Pk->k.alpha, Pk->k.vbeta, lane);   // (the exact pipeline borrowed the doubles)
+                    wide_factors(wv, ndk_row, Pk->k.n_k, cnt.dk(), mrow, Pk->w, Pk->k.alpha, Pk->k.vbeta, lane);   // (the exact pipeline borrowed the doubles)
                 }
               }
             }
             __builtin_amdgcn_s_setprio(0);
             if (lane == 0) {
 #ifdef ABL_WIDE_NOADDLOAD                                        // ablation (tools/abl_wide.py): no start-value loads behind the draw
-                const int nd0_z = 0, nk0_z = 1000;
+                const int2 st_z = make_int2(0, 1000);
 #else
-                const int nd0_z = ndk_row[zn], nk0_z = K.n_k[zn];   // (issued first: everything below up to their use overlaps them)
+                const int2 st_z = cnt.start(zn);                 // (issued first: everything below up to their use overlaps them)
 #endif
                 commit_site(K, i, v, f, zo, zn, cpos, KP);
                 const bool more = n + 1 < len;
                 // take the next site out of its topic already; when that is the topic just drawn the two changes must be
                 // applied in order (the factor is computed from the final count)
-                if (more && zo_c != zn) count_change(zo_c, -f_c, nd0_n, nk0_n);
-                count_change(zn, f, nd0_z, nk0_z);               // add the site back (LabeledLDA.py:121-125)
-                if (more && zo_c == zn) count_change(zo_c, -f_c, nd0_n, nk0_n);
+                if (more && ahead.zo_c != zn) count_change(ahead.zo_c, -ahead.f_c, st_n);
+                count_change(zn, f, st_z);                       // add the site back (LabeledLDA.py:121-125)
+                if (more && ahead.zo_c == zn) count_change(ahead.zo_c, -ahead.f_c, st_n);
             }
         };
         if constexpr (PREFETCH) {
@@ -955,26 +1033,9 @@ llda_sweep_wide_f32_kernel(const WParams P, const float margin0_rel, double *scr
         } else {
             for (int n = 0; n < len; ++n) site(n, xa, xb);
         }
-        for (int q = lane; q < KP4; q += 64) {
-            const int2 pk = reinterpret_cast<const int2 *>(s_dk)[q];
-            if (pk.x | pk.y) {
-                const int dl[4] = {(int)(int16_t)(pk.x & 0xFFFF), pk.x >> 16, (int)(int16_t)(pk.y & 0xFFFF), pk.y >> 16};
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (dl[j]) {
-                        atomicAdd(K.n_k_delta + ((q << 2) | j), dl[j]);
-                        ndk_row[(q << 2) | j] += dl[j];
-                    }
-            }
-        }
+        cnt.flush(lane, K.n_k_delta);
     }
-    if (lane == 0 && K.status) {                                 // statistics, as the narrow kernels
-        if (n_unsure) atomicAdd(K.status + 1, n_unsure);
-        if (n_exact) {
-            atomicOr(K.status, 2);
-            atomicAdd(K.status + 2, n_exact);
-        }
-    }
+    wide_report_status(K, lane, n_unsure, n_exact);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1120,6 +1181,35 @@ __device__ __forceinline__ void wide_load_lm(double *wv, const double *row, cons
     }
 }
 
+// the keyed uniform of site n of a document walked site by site: one Philox block serves sites 2b and 2b + 1; the 64 lanes
+// compute 64 consecutive blocks at once, every 128 sites, and hand them out (ctr3: the sweep, or 0xFFFFFFFF for prep4test)
+__device__ __forceinline__ double wide_foldin_uniform(const FParams &F, int n, uint32_t gdoc, uint32_t stream_id, uint32_t ctr3,
+                                                      int lane, uint32_t &r0, uint32_t &r1, uint32_t &r2, uint32_t &r3)
+{
+    if ((n & 127) == 0) {
+        r0 = (uint32_t)(n >> 1) + (uint32_t)lane; r1 = gdoc; r2 = stream_id; r3 = ctr3;
+        philox4x32_10(r0, r1, r2, r3, F.key0, F.key1);
+    }
+    const int holder = (n >> 1) & 63;
+    const uint32_t ra = (uint32_t)__shfl((int)((n & 1) ? r2 : r0), holder, 64);
+    const uint32_t rb = (uint32_t)__shfl((int)((n & 1) ? r3 : r1), holder, 64);
+    return uniform53(ra, rb);
+}
+
+// LabeledLDA.prep4test's draw of one site: the init row, `while prob.sum() > 1: prob /= c`, the keyed draw
+__device__ __forceinline__ int wide_init_draw(double *wv, const FParams &F, const WideLayout &W, int64_t site, double c, double c_rcp,
+                                          double u, int lane)
+{
+    wide_load_lm(wv, F.phn + (int64_t)F.init_idx[site] * W.KP, W, lane);
+    wide_shrink(wv, W, lane, c, c_rcp);
+    int zn = wide_draw(wv, W, u, lane);
+    if (zn < 0) {
+        zn = 0;
+        if (lane == 0 && F.status) atomicOr(F.status, 1);
+    }
+    return zn;
+}
+
 __global__ void __launch_bounds__(64) llda_foldin_init_wide_kernel(const WFParams P)
 {
     extern __shared__ double s_wide[];
@@ -1139,14 +1229,7 @@ __global__ void __launch_bounds__(64) llda_foldin_init_wide_kernel(const WFParam
         uint32_t r0 = (uint32_t)(n >> 1), r1 = gdoc, r2 = F.doc_stream ? F.doc_stream[d] : F.stream_id, r3 = 0xFFFFFFFFu;
         philox4x32_10(r0, r1, r2, r3, F.key0, F.key1);
         const uint32_t ra = (n & 1) ? r2 : r0, rb = (n & 1) ? r3 : r1;
-        const double u = ((double)(ra >> 5) * 67108864.0 + (double)(rb >> 6)) * (1.0 / 9007199254740992.0);
-        wide_load_lm(wv, F.phn + (int64_t)F.init_idx[site] * W.KP, W, lane);
-        wide_shrink(wv, W, lane, F.c_init, 1.0 / F.c_init);
-        int zn = wide_draw(wv, W, u, lane);
-        if (zn < 0) {
-            zn = 0;
-            if (lane == 0 && F.status) atomicOr(F.status, 1);
-        }
+        const int zn = wide_init_draw(wv, F, W, site, F.c_init, 1.0 / F.c_init, uniform53(ra, rb), lane);
         if (lane == 0) {
             int ln, sn;
             lane_slot_of_rt(W.G, W.T, zn, ln, sn);
@@ -1185,25 +1268,12 @@ __global__ void __launch_bounds__(64) llda_foldin_wide_kernel(const WFParams P)
         int ntot = 0;
         for (int n = 0; n < len; ++n) ntot += F.freq[s0 + n];
         const double c1 = F.c_loop, c1r = 1.0 / c1;
-        if (!pre) {                                         // prep4test: the statements of llda_foldin_init_wide_kernel
+        if (!pre) {                                         // prep4test, as llda_foldin_init_wide_kernel
             const double c0 = F.c_init, c0r = 1.0 / c0;
             uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
             for (int n = 0; n < len; ++n) {
-                if ((n & 127) == 0) {
-                    r0 = (uint32_t)(n >> 1) + (uint32_t)lane; r1 = gdoc; r2 = stream_id; r3 = 0xFFFFFFFFu;
-                    philox4x32_10(r0, r1, r2, r3, F.key0, F.key1);
-                }
-                const int holder = (n >> 1) & 63;
-                const uint32_t ra = (uint32_t)__shfl((int)((n & 1) ? r2 : r0), holder, 64);
-                const uint32_t rb = (uint32_t)__shfl((int)((n & 1) ? r3 : r1), holder, 64);
-                const double u = ((double)(ra >> 5) * 67108864.0 + (double)(rb >> 6)) * (1.0 / 9007199254740992.0);
-                wide_load_lm(wv, F.phn + (int64_t)F.init_idx[s0 + n] * KP, W, lane);
-                wide_shrink(wv, W, lane, c0, c0r);
-                int zn = wide_draw(wv, W, u, lane);
-                if (zn < 0) {
-                    zn = 0;
-                    if (lane == 0 && F.status) atomicOr(F.status, 1);
-                }
+                const double u = wide_foldin_uniform(F, n, gdoc, stream_id, 0xFFFFFFFFu, lane, r0, r1, r2, r3);
+                const int zn = wide_init_draw(wv, F, W, s0 + n, c0, c0r, u, lane);
                 if (lane == 0) {
                     s_ndk[zn] += F.freq[s0 + n];
                     F.z[s0 + n] = zn;
@@ -1215,14 +1285,7 @@ __global__ void __launch_bounds__(64) llda_foldin_wide_kernel(const WFParams P)
             uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
             for (int n = 0; n < len; ++n) {
                 const int v = F.word[s0 + n], f = F.freq[s0 + n];
-                if ((n & 127) == 0) {
-                    r0 = (uint32_t)(n >> 1) + (uint32_t)lane; r1 = gdoc; r2 = stream_id; r3 = (uint32_t)sweep;
-                    philox4x32_10(r0, r1, r2, r3, F.key0, F.key1);
-                }
-                const int holder = (n >> 1) & 63;
-                const uint32_t ra = (uint32_t)__shfl((int)((n & 1) ? r2 : r0), holder, 64);
-                const uint32_t rb = (uint32_t)__shfl((int)((n & 1) ? r3 : r1), holder, 64);
-                const double u = ((double)(ra >> 5) * 67108864.0 + (double)(rb >> 6)) * (1.0 / 9007199254740992.0);
+                const double u = wide_foldin_uniform(F, n, gdoc, stream_id, (uint32_t)sweep, lane, r0, r1, r2, r3);
                 const int zo = F.z[s0 + n];
                 if (lane == 0) s_ndk[zo] -= f;                                   // n_dk[z] -= f
                 const double *brow = ph + (int64_t)v * KP;
