@@ -1035,6 +1035,82 @@ int llda_frex_struct_bytes(void);
 int64_t llda_frex_scratch_bytes(int64_t V, int32_t n_labels, int32_t n);
 int llda_frex_select(const llda_frex_args *args, void *stream);
 
+/* EM training, the word side (additive to ABI 22): llda_attribute's E-step adds a site's label shares to its DOCUMENT; this adds
+ * the same shares to its WORD.  credit_w[v][k] is the expected n_kw of the corpus under (theta, phi_t); with llda_phi_step below it
+ * is the other half of an EM fit of Labeled LDA without random numbers.
+ *   word_off [V+1] int64, site_doc [S] int32, freq [S] int32 or NULL (= all 1; 0 <= f < 2^23): the sites in WORD-major order, a
+ *   CSR over the words: the sites of word v are word_off[v] .. word_off[v+1], site_doc their documents.  S = word_off[V], the
+ *   caller states it (0 <= S <= LLDA_WCREDIT_MAX_SITES); offsets outside [0, S] are not used as addresses;
+ *   theta [D][ld_theta] and phi_t [V][ld_phi] doubles, REFERENCE topic order, ld_* >= K.  Columns >= K are never read;
+ *   chunk >= 1: how many consecutive sites of a word are added up by one wavefront.
+ * A site (d, f) of word v, in the arithmetic of llda_attribute (every operation one IEEE float64 operation, rounded on its own;
+ * sum64 as defined there):  ok = d in [0, D) (a document id outside is never used as an index);  t[k] = theta[d][k] * phi_t[v][k];
+ * p = sum64(t).  The site is GOOD when it is ok and LLDA_ATTR_MIN_P <= p < inf.  A site that is not good adds f to bad[v] and
+ * nothing else.  A good site adds f to tok[v]; inv = 1.0 / p; g = (double)f * inv; acc[k] = acc[k] + t[k] * g.  (Multiplication
+ * commutes: t, p, inv and g carry the bits they have in llda_attribute.)
+ * The order of the sum: the sites of word v are cut into chunks of `chunk` consecutive sites, the last may be shorter.  A chunk is
+ * added in ascending site order from +0.0; credit_w[v][k] is the chunk sums added in ascending chunk order from +0.0.  A word
+ * without sites gets a row of +0.0 and tok = bad = 0.
+ *   credit_w [V][ld_credit] doubles, tok [V], bad [V] int64: each may be NULL.  Columns >= K of credit_w are not written.
+ * A word's outputs depend on its own sites, its own row of phi_t, the rows of theta they name and chunk -- not on V, the word's
+ * place in the batch, the grid or the kernel form -- and equal the restatement in tests/emref.py bit for bit.  No floating-point
+ * atomics: one wavefront (for K <= 32 a group of 8, 16 or 32 lanes) per chunk, phi_t's row in registers up to K = 1024 and read
+ * through its pointer beyond, with the sums in LDS; the only chunk of a word stores straight to the outputs, the chunks of a longer
+ * word store partial rows to the scratch, which a second pass adds.  A wavefront finds its chunk in a table (the word of every chunk,
+ * next to a prefix sum of the words' chunk counts) that a first one-workgroup pass leaves in the scratch.
+ *   scratch: llda_credit_words_scratch_bytes(V, S, K, chunk) bytes = 16 (V + 1) + 2 floor(S / chunk) (8 K + 16) + 4 C rounded up to
+ *   a multiple of 8 + 16, C = min(S, floor(S / chunk) + V) the chunks at most.
+ * S == 0 still writes the zero rows and needs no input and no scratch; with every output NULL nothing is launched.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a struct_bytes that is not the struct's; D < 0; V outside
+ * 1 .. 2^31 - 1; S outside 0 .. LLDA_WCREDIT_MAX_SITES; an ld < K; chunk < 1; with S > 0 a NULL word_off, site_doc, phi_t or
+ * scratch, a NULL theta (D > 0), or scratch_bytes below the query; a misaligned pointer.  All before anything touches HIP. */
+#define LLDA_WCREDIT_MAX_SITES (1LL << 40)
+typedef struct llda_wcredit_args {
+    uint32_t struct_bytes;       /* sizeof(llda_wcredit_args)                                    */
+    int32_t  K, chunk, reserved;
+    const int64_t *word_off;     /* [dev] [V+1]                                                  */
+    const int32_t *site_doc;     /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S] or NULL                                            */
+    const double  *theta;        /* [dev] [D][ld_theta]                                          */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    int64_t  D, V, S, ld_theta, ld_phi, ld_credit;
+    double  *credit_w;           /* [dev] [V][ld_credit] or NULL                                 */
+    int64_t *tok;                /* [dev] [V] or NULL                                            */
+    int64_t *bad;                /* [dev] [V] or NULL                                            */
+    void    *scratch;            /* [dev] work space                                             */
+    int64_t  scratch_bytes;
+} llda_wcredit_args;
+int llda_wcredit_struct_bytes(void);
+int64_t llda_credit_words_scratch_bytes(int64_t V, int64_t S, int32_t K, int32_t chunk);
+int llda_credit_words(const llda_wcredit_args *args, void *stream);
+
+/* EM training, the phi M-step (additive to ABI 22): the shape of the reference's get_phi, (n + b) / (n_k + V b), on expected counts.
+ *   cw [V][ld] doubles: the word credit (non-negative, finite); beta > 0, finite.
+ *   colsum[k]: the rows are cut into blocks of LLDA_COLSUM_ROWS consecutive words; a block is added in ascending word order from
+ *   +0.0, the block sums in ascending block order from +0.0.  Vb = (double)V * beta, rounded once; den[k] = colsum[k] + Vb;
+ *   phi_t_out[v][k] = (cw[v][k] + beta) / den[k].  Every operation one IEEE float64 operation; tests/emref.py restates it.
+ *   phi_t_out [V][ld_out] doubles: may be cw itself with ld_out = ld (an entry is read and written by one thread, after the sums);
+ *   den [K] doubles or NULL.  Columns >= K are neither read nor written.
+ *   scratch: llda_phi_step_scratch_bytes(V, K) bytes = (ceil(V / 256) + 1) 8 K + 16, the block sums and den.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a wrong struct_bytes; V outside 1 .. 2^31 - 1; an ld < K;
+ * beta not a finite number > 0; a NULL cw, phi_t_out or scratch; scratch_bytes below the query; a misaligned pointer.  All before
+ * anything touches HIP. */
+#define LLDA_COLSUM_ROWS 256
+typedef struct llda_phistep_args {
+    uint32_t struct_bytes;       /* sizeof(llda_phistep_args)                                    */
+    int32_t  K;
+    const double *cw;            /* [dev] [V][ld]                                                */
+    double  *phi_t_out;          /* [dev] [V][ld_out]                                            */
+    double  *den;                /* [dev] [K] or NULL                                            */
+    int64_t  V, ld, ld_out;
+    double   beta;
+    void    *scratch;            /* [dev] work space                                             */
+    int64_t  scratch_bytes;
+} llda_phistep_args;
+int llda_phistep_struct_bytes(void);
+int64_t llda_phi_step_scratch_bytes(int64_t V, int32_t K);
+int llda_phi_step(const llda_phistep_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -289,6 +289,44 @@ class LabeledLDA(object):
             if bad & _native.READOUT_NO_LOAD:
                 raise ValueError('A word in dictionary has no z-value')
 
+    def fit_em(self, iters=50, theta_steps=1, start="counts", chunk=4096, trace_every=0):
+        """Fit ``ph_hat`` / ``th_hat`` by EM on the device, without random numbers (``emfit.fit``): ``iters`` passes
+        of the theta M-step (``theta_steps`` steps of llda_attribute with alpha), the word-side E-step (llda_credit_words) and the
+        phi M-step (llda_phi_step with beta).  start = "counts": from ``get_theta()`` / ``get_phi()`` of the current counts (the
+        random initial assignments break the symmetry between labels that always occur together); "ph_hat": from the running
+        means.  Theta is 0 outside a document's labels at the start and stays 0.  The result goes to ``ph_hat`` / ``th_hat`` and the
+        hats count as filled: ``word_credit``, ``fold_in_em``, ``predict_em``, ``heldout_perplexity``, ``left_to_right`` and
+        ``label_words(source="ph_hat")`` read the EM estimates, and ``cur_perplx`` gets the perplexity of the training sites under
+        them.  z, the counts, the priors and the draw keys are not touched: a later ``run_training`` continues the chain as if this
+        had not been called, and its first thinning read-out starts the running means afresh.  trace_every = n > 0: the data term
+        sum f log p every n iterations.  Returns dict(iterations=iters, trace=[(iteration, loglik, tokens, bad), ...]).
+        One device only: with several ranks it raises."""
+        import torch
+        from . import emfit, heldout
+        if _world_size() > 1:
+            raise ValueError("fit_em runs on one device only: it was called with %d ranks" % _world_size())
+        if start not in ("counts", "ph_hat"):
+            raise ValueError("start must be 'counts' or 'ph_hat'")
+        sm = self._sampler
+        sm.check_status()
+        dev = sm.device
+        if start == "counts" or not self.cur_perplx:
+            th0, ph0 = sm.theta(), sm.phi()
+        else:
+            ph0 = self._ph_hat.dev if self._ph_hat.dev is not None else torch.from_numpy(np.ascontiguousarray(self.ph_hat, dtype=np.float64))
+            th0 = self._th_hat.dev if self._th_hat.dev is not None else torch.from_numpy(np.ascontiguousarray(self.th_hat, dtype=np.float64))
+        doc_off, word, freq = csr_from_doc_tups(self.doc_tups)
+        r = emfit.fit(th0.to(dev), ph0.to(dev).t().contiguous(), doc_off, word, freq, float(self.alpha), float(self.beta), iters,
+                      theta_steps=theta_steps, chunk=chunk, trace_every=trace_every)
+        self._ph_hat.set(None)
+        self._ph_hat.dev = r["phi_t"].t().contiguous()
+        self._th_hat.set(None)
+        self._th_hat.dev = r["theta"]
+        mant, expo, tok, bad = heldout.loglik(r["theta"], r["phi_t"], doc_off, word, freq, weighted=False)
+        s = heldout.perplexity_from(mant, expo, tok, bad)
+        self.cur_perplx.append(float(np.exp(-s["loglik"] / max(s["tokens"], 1))))     # (sites unweighted, as in ``perplexity``)
+        return dict(iterations=r["iterations"], trace=r["trace"])
+
     # ---- read-outs ----
     def get_phi(self):
         """(n_k_v + beta) / (n_zk + V*beta): reference LabeledLDA.py:231-234 (llda_readout_phi)."""
@@ -885,11 +923,15 @@ def prune_dict(docs, lower=0.1, upper=0.9):
     return dicti
 
 
-def train_it(traindata, it=30, s=3, al=0.001, be=0.001, l=0.05, u=0.95):
+def train_it(traindata, it=30, s=3, al=0.001, be=0.001, l=0.05, u=0.95, em=0):
+    """em = n > 0: fit by ``fit_em(n)`` in place of ``run_training(it, s)``"""
     a, b, c = traindata
     dicti = prune_dict(a, lower=l, upper=u)
     llda = LabeledLDA(a, b, c, dicti, al, be)
-    llda.run_training(it, s)
+    if em > 0:
+        llda.fit_em(em)
+    else:
+        llda.run_training(it, s)
     return llda
 
 

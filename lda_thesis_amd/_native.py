@@ -142,6 +142,20 @@ class LldaFrexArgs(ctypes.Structure):
                 ("scratch_bytes", _c_i64)]
 
 
+class LldaWcreditArgs(ctypes.Structure):
+    """struct llda_wcredit_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("chunk", _c_i32), ("reserved", _c_i32), ("word_off", _c_p), ("site_doc", _c_p),
+                ("freq", _c_p), ("theta", _c_p), ("phi_t", _c_p), ("D", _c_i64), ("V", _c_i64), ("S", _c_i64), ("ld_theta", _c_i64),
+                ("ld_phi", _c_i64), ("ld_credit", _c_i64), ("credit_w", _c_p), ("tok", _c_p), ("bad", _c_p), ("scratch", _c_p),
+                ("scratch_bytes", _c_i64)]
+
+
+class LldaPhistepArgs(ctypes.Structure):
+    """struct llda_phistep_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("cw", _c_p), ("phi_t_out", _c_p), ("den", _c_p), ("V", _c_i64), ("ld", _c_i64),
+                ("ld_out", _c_i64), ("beta", _c_d), ("scratch", _c_p), ("scratch_bytes", _c_i64)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -153,7 +167,9 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_label_struct_bytes", "llda_label_scratch_bytes", "llda_label_metrics", "llda_sets_struct_bytes", "llda_label_sets",
            "llda_scored_struct_bytes", "llda_scored_words_scratch_bytes", "llda_scored_words",
            "llda_ecdf_struct_bytes", "llda_ecdf_scratch_bytes", "llda_ecdf_ranks",
-           "llda_frex_struct_bytes", "llda_frex_scratch_bytes", "llda_frex_select")
+           "llda_frex_struct_bytes", "llda_frex_scratch_bytes", "llda_frex_select",
+           "llda_wcredit_struct_bytes", "llda_credit_words_scratch_bytes", "llda_credit_words",
+           "llda_phistep_struct_bytes", "llda_phi_step_scratch_bytes", "llda_phi_step")
 
 _LIB = None
 
@@ -275,6 +291,18 @@ def lib():
     L.llda_frex_scratch_bytes.argtypes = [_c_i64, _c_i32, _c_i32]
     L.llda_frex_select.restype = ctypes.c_int
     L.llda_frex_select.argtypes = [ctypes.POINTER(LldaFrexArgs), _c_p]
+    L.llda_wcredit_struct_bytes.restype = ctypes.c_int
+    L.llda_wcredit_struct_bytes.argtypes = []
+    L.llda_credit_words_scratch_bytes.restype = _c_i64
+    L.llda_credit_words_scratch_bytes.argtypes = [_c_i64, _c_i64, _c_i32, _c_i32]
+    L.llda_credit_words.restype = ctypes.c_int
+    L.llda_credit_words.argtypes = [ctypes.POINTER(LldaWcreditArgs), _c_p]
+    L.llda_phistep_struct_bytes.restype = ctypes.c_int
+    L.llda_phistep_struct_bytes.argtypes = []
+    L.llda_phi_step_scratch_bytes.restype = _c_i64
+    L.llda_phi_step_scratch_bytes.argtypes = [_c_i64, _c_i32]
+    L.llda_phi_step.restype = ctypes.c_int
+    L.llda_phi_step.argtypes = [ctypes.POINTER(LldaPhistepArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -294,7 +322,9 @@ def lib():
                                                                                      L.llda_nearest_struct_bytes()))
     for name, struct, size in (("LldaLabelArgs", LldaLabelArgs, L.llda_label_struct_bytes()), ("LldaSetsArgs", LldaSetsArgs, L.llda_sets_struct_bytes()),
                                ("LldaScoredArgs", LldaScoredArgs, L.llda_scored_struct_bytes()),
-                               ("LldaEcdfArgs", LldaEcdfArgs, L.llda_ecdf_struct_bytes()), ("LldaFrexArgs", LldaFrexArgs, L.llda_frex_struct_bytes())):
+                               ("LldaEcdfArgs", LldaEcdfArgs, L.llda_ecdf_struct_bytes()), ("LldaFrexArgs", LldaFrexArgs, L.llda_frex_struct_bytes()),
+                               ("LldaWcreditArgs", LldaWcreditArgs, L.llda_wcredit_struct_bytes()),
+                               ("LldaPhistepArgs", LldaPhistepArgs, L.llda_phistep_struct_bytes())):
         if size != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
@@ -612,6 +642,47 @@ def attribute(doc_off, word, freq, theta, phi_t, D, V, K, *, iters=0, alpha=0.0,
                      int(K), int(iters), int(top_m), 0, float(alpha), _ptr(theta_out), _ptr(credit), _ptr(site_idx), _ptr(site_val),
                      _ptr(tok), _ptr(bad))
     _launch(theta, lib().llda_attribute, "llda_attribute", ctypes.byref(a))
+
+
+COLSUM_ROWS = 256              # LLDA_COLSUM_ROWS: words of a block of llda_phi_step's column sums
+
+
+def credit_words_scratch_bytes(V, S, K, chunk):
+    """llda_credit_words_scratch_bytes: bytes of work space llda_credit_words needs (host only)."""
+    r = int(lib().llda_credit_words_scratch_bytes(int(V), int(S), int(K), int(chunk)))
+    if r < 0:
+        check(r, "llda_credit_words_scratch_bytes(V=%d, S=%d, K=%d, chunk=%d)" % (V, S, K, chunk))
+    return r
+
+
+def credit_words(word_off, site_doc, freq, theta, phi_t, D, V, S, K, chunk, scratch, *, ld_theta=None, ld_phi=None, ld_credit=None,
+                 credit_w=None, tok=None, bad=None):
+    """llda_credit_words on the current torch stream: word_off (int64 [V+1]) / site_doc (int32 [S]) / freq (int32 [S] or None) the
+    sites in word-major order; theta (D, ld_theta) and phi_t (V, ld_phi) float64; credit_w (V, ld_credit) float64, tok, bad (int64
+    [V]) the outputs, each may be None; scratch = a uint8 tensor of credit_words_scratch_bytes(V, S, K, chunk) bytes (None: S = 0)."""
+    a = LldaWcreditArgs(ctypes.sizeof(LldaWcreditArgs), int(K), int(chunk), 0, _ptr(word_off), _ptr(site_doc), _ptr(freq), _ptr(theta),
+                        _ptr(phi_t), int(D), int(V), int(S), int(theta.stride(0) if ld_theta is None else ld_theta),
+                        int(phi_t.stride(0) if ld_phi is None else ld_phi),
+                        int(K if credit_w is None else credit_w.stride(0)) if ld_credit is None else int(ld_credit),
+                        _ptr(credit_w), _ptr(tok), _ptr(bad), _ptr(scratch), 0 if scratch is None else int(scratch.numel()))
+    _launch(phi_t, lib().llda_credit_words, "llda_credit_words", ctypes.byref(a))
+
+
+def phi_step_scratch_bytes(V, K):
+    """llda_phi_step_scratch_bytes: bytes of work space llda_phi_step needs (host only)."""
+    r = int(lib().llda_phi_step_scratch_bytes(int(V), int(K)))
+    if r < 0:
+        check(r, "llda_phi_step_scratch_bytes(V=%d, K=%d)" % (V, K))
+    return r
+
+
+def phi_step(cw, V, K, beta, out, scratch, *, ld=None, ld_out=None, den=None):
+    """llda_phi_step on the current torch stream: cw (V, ld) float64 the word credit, out (V, ld_out) float64 the new phi_t (may be
+    cw), den (float64 [K]) or None; scratch = a uint8 tensor of phi_step_scratch_bytes(V, K) bytes."""
+    a = LldaPhistepArgs(ctypes.sizeof(LldaPhistepArgs), int(K), _ptr(cw), _ptr(out), _ptr(den), int(V),
+                        int(cw.stride(0) if ld is None else ld), int(out.stride(0) if ld_out is None else ld_out), float(beta),
+                        _ptr(scratch), int(scratch.numel()))
+    _launch(cw, lib().llda_phi_step, "llda_phi_step", ctypes.byref(a))
 
 
 LR_MAX_PARTICLES = 16          # LLDA_LR_MAX_PARTICLES

@@ -56,6 +56,8 @@
 //                       llda_label_sets_kernel   per-label thresholds applied to every document: masks by ballot, tp / fp / fn
 //   kernel_ecdf.hpp     llda_ecdf_totals / _keys / _walk kernels   every word's ECDF rank within every topic, on kernel_label.hpp's sort
 //                       llda_frex_select_kernel, llda_frex_merge_kernel   the n best words of every topic by two ranks (FREX): exact 96-bit compares
+//   kernel_emfit.hpp    llda_wcredit_index / _wave / _lds / _group / _combine kernels   the E-step's shares added up per word, in chunks of a word's sites
+//                       llda_phistep_block / _den / _div kernels   the phi M-step: column sums in a fixed order, one division per entry
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -97,6 +99,7 @@
 #include "kernel_nearest.hpp"
 #include "kernel_label.hpp"
 #include "kernel_ecdf.hpp"
+#include "kernel_emfit.hpp"
 
 namespace {
 
@@ -458,6 +461,34 @@ int launch_attr(const AttrParams &P, hipStream_t st)
             return launched();
         });
 }
+
+// llda_credit_words: the chunk kernel by K (kernel_emfit.hpp), on at most `chunks` chunks
+int launch_wcredit(const WCreditParams &P, int64_t chunks, hipStream_t st)
+{
+    const dim3 block(64 * WCREDIT_WAVES);
+    const DocGeom g = doc_geom(P.K);
+    if (g.G) return visit_int<8, 16, 32>(g.G, [&](auto G) {
+        constexpr int per = 64 * WCREDIT_WAVES / G.value;
+        hipLaunchKernelGGL(llda_wcredit_group_kernel<G.value>, doc_grid((chunks + per - 1) / per), block, 0, st, P);
+        return launched();
+    });
+    if (g.NI) return visit_int<1, 2, 4, 8, 16>(g.NI, [&](auto NI) {
+        hipLaunchKernelGGL((llda_wcredit_wave_kernel<NI.value, attr_u(NI.value)>), doc_grid((chunks + WCREDIT_WAVES - 1) / WCREDIT_WAVES), block, 0, st, P);
+        return launched();
+    });
+    const size_t lds = (size_t)P.K * sizeof(double);                             // the chunk's sums: at most 61 504 bytes
+    const int rl = allow_lds(llda_wcredit_lds_kernel, lds);
+    if (rl) return rl;
+    hipLaunchKernelGGL(llda_wcredit_lds_kernel, doc_grid(chunks, WCREDIT_LDS_MAX_BLOCKS), dim3(64), lds, st, P);
+    return launched();
+}
+
+// partial rows of llda_credit_words at most: a word with more than one chunk has more than `chunk` sites, so its chunks are fewer
+// than twice its share of S / chunk
+inline int64_t wcredit_rows(int64_t S, int32_t chunk) { return 2 * (S / chunk); }
+
+// chunks of llda_credit_words at most: a word's last chunk may be short, and there are never more chunks than sites
+inline int64_t wcredit_chunks_cap(int64_t V, int64_t S, int32_t chunk) { const int64_t most = S / chunk + V; return most < S ? most : S; }
 
 }  // namespace
 
@@ -1388,6 +1419,88 @@ int llda_frex_select(const llda_frex_args *a, void *stream)
         hipLaunchKernelGGL(llda_frex_merge_kernel<N.value>, merge_grid, dim3(64), 0, st, P);
         return launched();
     });
+}
+
+int llda_wcredit_struct_bytes(void) { return (int)sizeof(llda_wcredit_args); }
+int llda_phistep_struct_bytes(void) { return (int)sizeof(llda_phistep_args); }
+
+int64_t llda_credit_words_scratch_bytes(int64_t V, int64_t S, int32_t K, int32_t chunk)
+{
+    if (V < 1 || V > INT32_MAX || S < 0 || S > LLDA_WCREDIT_MAX_SITES || K < 1 || K > LLDA_MAX_K || chunk < 1) return LLDA_E_BAD_ARG;
+    return 16 * (V + 1) + wcredit_rows(S, chunk) * (8 * (int64_t)K + 16) + (4 * wcredit_chunks_cap(V, S, chunk) + 7) / 8 * 8 + 16;    // (below 2^58)
+}
+
+int llda_credit_words(const llda_wcredit_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_wcredit_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->S < 0 || a->S > LLDA_WCREDIT_MAX_SITES || a->chunk < 1) return LLDA_E_BAD_ARG;
+    if (a->ld_theta < a->K || a->ld_phi < a->K || a->ld_credit < a->K) return LLDA_E_BAD_ARG;
+    if (a->D > INT64_MAX / a->ld_theta || a->V > INT64_MAX / a->ld_phi || a->V > INT64_MAX / a->ld_credit) return LLDA_E_BAD_ARG;
+    if (a->S > 0 && (!a->word_off || !a->site_doc || !a->phi_t || !a->scratch || (a->D > 0 && !a->theta))) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->word_off, a->theta, a->phi_t, a->credit_w, a->tok, a->bad) || misaligned(7, a->scratch) || misaligned(3, a->site_doc, a->freq))
+        return LLDA_E_BAD_ARG;
+    const int64_t need = llda_credit_words_scratch_bytes(a->V, a->S, a->K, a->chunk);
+    if (a->S > 0 && (need < 0 || a->scratch_bytes < need)) return LLDA_E_BAD_ARG;
+    if (!a->credit_w && !a->tok && !a->bad) return LLDA_OK;
+    WCreditParams P;
+    memset(&P, 0, sizeof P);
+    P.word = a->site_doc; P.freq = a->freq; P.K = a->K;
+    // the rows that stream in are theta's.  No document at all: every site is not ok and reads row 0 "in its place", which is phi_t's
+    P.phi_t = a->D > 0 ? a->theta : a->phi_t; P.ld_phi = a->D > 0 ? a->ld_theta : a->ld_phi; P.V = a->D;
+    P.word_off = a->word_off; P.wphi = a->phi_t; P.n_words = a->V; P.ld_wphi = a->ld_phi; P.ld_credit = a->ld_credit;
+    P.S = a->S; P.chunk = a->chunk; P.rows_cap = wcredit_rows(a->S, a->chunk);
+    P.credit_w = a->credit_w; P.tok = a->tok; P.bad = a->bad;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->S > 0) {
+        P.cfirst = static_cast<int64_t *>(a->scratch);
+        P.pfirst = P.cfirst + (a->V + 1);
+        P.ptok = P.pfirst + (a->V + 1);
+        P.pbad = P.ptok + P.rows_cap;
+        P.part = reinterpret_cast<double *>(P.pbad + P.rows_cap);
+        P.cword = reinterpret_cast<int32_t *>(P.part + P.rows_cap * a->K);
+        P.chunks_cap = wcredit_chunks_cap(a->V, a->S, a->chunk);
+        hipLaunchKernelGGL(llda_wcredit_index_kernel, dim3(1), dim3(WCREDIT_INDEX_NT), 0, st, P);
+        const int rc = launch_wcredit(P, P.chunks_cap, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(llda_wcredit_combine_kernel, doc_grid((a->V + WCREDIT_WAVES - 1) / WCREDIT_WAVES), dim3(64 * WCREDIT_WAVES), 0, st, P);
+    return launched();
+}
+
+int64_t llda_phi_step_scratch_bytes(int64_t V, int32_t K)
+{
+    if (V < 1 || V > INT32_MAX || K < 1 || K > LLDA_MAX_K) return LLDA_E_BAD_ARG;
+    return ((V + PHISTEP_ROWS - 1) / PHISTEP_ROWS + 1) * 8 * (int64_t)K + 16;
+}
+
+int llda_phi_step(const llda_phistep_args *a, void *stream)
+{
+    static_assert(PHISTEP_ROWS == LLDA_COLSUM_ROWS, "kernel_emfit.hpp restates the header");
+    if (!a || a->struct_bytes != sizeof(llda_phistep_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->V < 1 || a->V > INT32_MAX || a->ld < a->K || a->ld_out < a->K) return LLDA_E_BAD_ARG;
+    if (!(a->beta > 0.0) || !(a->beta < INFINITY)) return LLDA_E_BAD_ARG;
+    if (!a->cw || !a->phi_t_out || !a->scratch) return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / 8 / a->ld || a->V > INT64_MAX / 8 / a->ld_out) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->cw, a->phi_t_out, a->den) || misaligned(7, a->scratch)) return LLDA_E_BAD_ARG;
+    const int64_t need = llda_phi_step_scratch_bytes(a->V, a->K);
+    if (need < 0 || a->scratch_bytes < need) return LLDA_E_BAD_ARG;
+    PhiStepParams P;
+    memset(&P, 0, sizeof P);
+    P.cw = a->cw; P.out = a->phi_t_out; P.den_out = a->den;
+    P.V = a->V; P.ld = a->ld; P.ld_out = a->ld_out; P.K = a->K;
+    P.n_blocks = (a->V + PHISTEP_ROWS - 1) / PHISTEP_ROWS;
+    P.bsum = static_cast<double *>(a->scratch);
+    P.den = P.bsum + P.n_blocks * a->K;
+    P.beta = a->beta; P.Vb = (double)a->V * a->beta;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned kb = (unsigned)((a->K + PHISTEP_NT - 1) / PHISTEP_NT);
+    hipLaunchKernelGGL(llda_phistep_block_kernel, dim3((unsigned)P.n_blocks, kb), dim3(PHISTEP_NT), 0, st, P);
+    hipLaunchKernelGGL(llda_phistep_den_kernel, dim3(kb), dim3(PHISTEP_NT), 0, st, P);
+    const int64_t blocks = (a->V * a->K + PHISTEP_NT - 1) / PHISTEP_NT;
+    hipLaunchKernelGGL(llda_phistep_div_kernel, doc_grid(blocks, 1 << 16), dim3(PHISTEP_NT), 0, st, P);
+    return launched();
 }
 
 int llda_loglik(const int64_t *doc_off, const int32_t *word, const uint16_t *lab_mask, const int32_t *n_dk,

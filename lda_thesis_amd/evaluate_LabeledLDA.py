@@ -55,6 +55,9 @@ def build_parser():
     p.add_option("--em-foldin", dest="em_foldin", type="int", default=0, metavar="ITERS",
                  help="after the report: the same four metrics for the loads of the deterministic EM fold-in with ITERS steps "
                       "(llda_attribute), ranked and scored on the GPU")
+    p.add_option("--em-train", dest="em_train", type="int", default=0, metavar="ITERS",
+                 help="fit the model by ITERS passes of deterministic EM (llda_attribute, llda_credit_words, llda_phi_step) in place "
+                      "of the Gibbs sweeps of -i / -s, which then only set the fold-in of the test documents")
     p.add_option("--explain", dest="explain", type="int", default=0, metavar="N",
                  help="after the report: for the first N test documents the suggested labels with the five most-credited words "
                       "of each (llda_attribute)")
@@ -289,7 +292,7 @@ def main(argv=None):
         opt.thinning = opt.it
     train, test = split_data(f=opt.file, d=opt.lvl)
     print("Starting training...")
-    model = train_it(train, it=opt.it, s=opt.thinning, al=opt.alpha, be=opt.beta, l=opt.lower, u=opt.upper)
+    model = train_it(train, it=opt.it, s=opt.thinning, al=opt.alpha, be=opt.beta, l=opt.lower, u=opt.upper, em=opt.em_train)
     print("Testing test data, this may take a while...")
     th, _ = test_it(model, test, it=opt.it, thinning=opt.thinning)
     th = np.array(th)
