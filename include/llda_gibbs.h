@@ -273,7 +273,10 @@ int llda_sweep(const llda_sweep_args *args, void *stream);
  * Arithmetic: one lane per ALLOWED topic (every instance of a launch has <= `lanes` allowed topics, lanes in
  * {8, 16, 32, 64}); the draw is decided from unnormalised fp64 prefix sums with a 2^-40 margin (it then equals the
  * reference pipeline's choice); a site that cannot be decided that way (~1e-11 per site) goes through
- * the reference's exact fp64 pipeline inside the kernel (status word 2 counts them).  Needs alpha, beta >= 1e-6,
+ * the reference's exact fp64 pipeline inside the kernel (status word 2 counts them).  An instance without an allowed
+ * topic (live_off[i+1] == live_off[i]) is legal: each of its sites has total 0, takes the exact tier, finds no topic with
+ * a positive probability and keeps its z -- bit 0 of status word 0 is set, n_dk and delta get nothing from it.
+ * Needs alpha, beta >= 1e-6,
  * V*beta < 2^40 (LLDA_E_BAD_ARG otherwise) and K_p <= 128 for every problem (the caller's responsibility). */
 typedef struct llda_batch_args {
     const int64_t *inst_off;     /* [dev] [I+1] site offsets of all document instances               */

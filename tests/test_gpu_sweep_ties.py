@@ -11,7 +11,8 @@ with -1 every site goes through the exact pipeline.
 
 Failing cases on the MI355X when this file was written: none in any family (general 15 cases, quad 5, sparse-label 7, wide 3, batched 2:
 0 of 32 -- the kernels leave the oracle's state and the status words of the table at every margin).  The two wide cases added since
-(the largest K of five and of seven tiers: the scan's carry over more than four tiers) pass as well.
+(the largest K of five and of seven tiers: the scan's carry over more than four tiers) pass as well, and so do the two mixed-wave cases
+of the batched kernel (test_batched_mixed_waves; with exact_call reading K from lane 0 of the wavefront both fail).
 """
 import numpy as np
 import pytest
@@ -103,14 +104,11 @@ def test_wide_layouts(c_oracle, K, dense):
     _status_words(s, status, tier0=(0, -6, -7))
 
 
-@pytest.mark.parametrize("margin", [0, -1])
-def test_batched_kernel(c_oracle, margin):
-    """llda_sweep_batch_kernel: one Ensemble of four sub-problems (K = 5, 60, 128, 100: lane classes 8, 16, 32, 64), each sub-problem's
-    documents a planted state of its K under SubLDA's key (stream = index of the sub-problem, documents counted from 0), all over one
-    vocabulary.  The Ensemble counts its state from the assignments, so the planted counts are written over it."""
+def _planted_ensemble(subs, streams=None):
+    """one Ensemble over the sub-problems ``subs`` (planted states over one vocabulary, each with its own word range).  The Ensemble
+    counts its state from the assignments, so the planted counts are written over it."""
     import torch
     from lda_thesis_amd.ensemble import Ensemble
-    subs = [st.batch_state(i) for i in range(len(st.BATCH))]
     V, alpha, beta = subs[0]["V"], subs[0]["alpha"], subs[0]["beta"]
     assert all(s["V"] == V for s in subs) and sum(int(s["doc_off"][-1]) for s in subs) == V
     lens = np.concatenate([np.diff(s["doc_off"]) for s in subs])
@@ -127,8 +125,7 @@ def test_batched_kernel(c_oracle, margin):
             allowed[d, :n_allowed[d]] = np.flatnonzero(s["labs"][d])
         plans.append(dict(K=K, docs=np.arange(d0, d0 + D, dtype=np.int64), allowed=allowed, n_allowed=n_allowed))
         d0 += D
-    ens = Ensemble(plans, [s["z"] for s in subs], doc_off, word, freq, V, alpha, beta, st.SEED)
-    assert [g for g, _ in ens.orders] == [8, 16, 32, 64]
+    ens = Ensemble(plans, [s["z"] for s in subs], doc_off, word, freq, V, alpha, beta, st.SEED, streams=streams)
     for i, s in enumerate(subs):                         # the planted counts in the device's position order
         kp, tp = int(ens._kp_h[i]), torch.from_numpy(ens._layouts[plans[i]["K"]].topic_pos.astype(np.int64)).to(ens.device)
         D = s["labs"].shape[0]
@@ -147,9 +144,10 @@ def test_batched_kernel(c_oracle, margin):
         got = ens.problem_state(i)
         for a, b in zip(got, (s["n_k_v"], s["n_d_k"], s["n_zk"], s["z"])):
             np.testing.assert_array_equal(a, b)
-    ens.debug_margin = margin
-    ens.sweep()
-    ens.check_status()
+    return ens
+
+
+def _equals_the_oracle(c_oracle, ens, subs):
     for i, s in enumerate(subs):
         cs = _oracle(c_oracle, s)
         n_k_v, n_d_k, n_zk, z = ens.problem_state(i)
@@ -158,7 +156,62 @@ def test_batched_kernel(c_oracle, margin):
         np.testing.assert_array_equal(n_d_k, cs.n_d_k, err_msg=what)
         np.testing.assert_array_equal(n_k_v, cs.n_k_v, err_msg=what)
         np.testing.assert_array_equal(n_zk, cs.n_zk, err_msg=what)
+
+
+@pytest.mark.parametrize("margin", [0, -1])
+def test_batched_kernel(c_oracle, margin):
+    """llda_sweep_batch_kernel: one Ensemble of four sub-problems (K = 5, 60, 128, 100: lane classes 8, 16, 32, 64), each sub-problem's
+    documents a planted state of its K under SubLDA's key (stream = index of the sub-problem, documents counted from 0), all over one
+    vocabulary."""
+    subs = [st.batch_state(i) for i in range(len(st.BATCH))]
+    V = subs[0]["V"]
+    ens = _planted_ensemble(subs)
+    assert [g for g, _ in ens.orders] == [8, 16, 32, 64]
+    ens.debug_margin = margin
+    ens.sweep()
+    ens.check_status()
+    _equals_the_oracle(c_oracle, ens, subs)
     if margin == 0:                                      # the kernel's one margin is tier 1's: exactly the ties take the exact pipeline
         assert int(ens.status[2]) == sum(s["n_ties"] for s in subs)
     else:
         assert int(ens.status[2]) == V
+
+
+@pytest.mark.parametrize("margin", [0, -1])
+def test_batched_mixed_waves(c_oracle, margin):
+    """llda_sweep_batch_kernel with lane groups of DIFFERENT sub-problems in one wavefront: the sub-problems of sweepties.BATCH_MIXED
+    share a lane class but not a layout (K = 100 with 128 and 60 with 64: the same KP, another tail; 96: another KP), and the launches
+    are made directly with the interleaved ``order`` of sweepties.mixed_order -- neighbouring groups never share a problem, every
+    wavefront holds planted and random documents.  The exact tier reads the dense layout of the group it serves from that group's lanes
+    (exact_call); with a neighbour's K the planted ties go wrong (model (f) of tests/test_sweep_ties_host.py)."""
+    import batchdirect as bd
+    from helpers import OracleBackend
+    from lda_thesis_amd import _native
+    subs = [st.mixed_state(i) for i in range(len(st.MIXED_SUBS))]
+    ens = _planted_ensemble(subs, streams=[m[5] for m in st.MIXED_SUBS])
+    assert [g for g, _ in ens.orders] == [lanes for lanes, _, _ in st.BATCH_MIXED]
+    # z, n_dk and delta in buffers with guard words before and behind; every launch compared as WHOLE buffers -- the padding positions
+    # of the rows and delta before the fold included -- with the C oracle run problem by problem on CPU copies of the same tensors
+    r = bd.Run.of(ens, _native)
+    backend = OracleBackend(c_oracle)
+    start = np.concatenate(([0], np.cumsum(ens._n_docs_h)))
+    want = r.host()
+    for g, (lanes, D, _) in enumerate(st.BATCH_MIXED):
+        order = np.array([start[i] + d for i, d in st.mixed_order(g)], dtype=np.int32)
+        assert sorted(order.tolist()) == sorted(ens.orders[g][1].cpu().tolist())          # Ensemble's launch of the class, in another order
+        r.oracle_launch(backend, want, order)
+        r.launch(order, lanes, margin)
+        r.check(want, "mixed waves, lanes %d, margin %d" % (lanes, margin))            # (counts unchanged by the launch, guards intact)
+    assert int((want["delta"] != 0).sum()) > 0
+    r.fold()
+    backend.apply_delta(want["counts"], want["delta"])
+    r.check(want, "mixed waves after the fold")
+    ens.check_status()
+    _equals_the_oracle(c_oracle, ens, subs)              # ... and every sub-problem on its own, a whole sweep of the C oracle
+    agg = dict(doc_off=np.array([0, ens.S]), n_ties=sum(s["n_ties"] for s in subs), n_outside=sum(s["n_outside"] for s in subs))
+    status = ens.status.cpu().numpy()
+    assert int(status[1]) == 0                           # (the batched kernel has no fp32 tier: nothing is handed over by one)
+    if margin == 0:
+        assert int(status[2]) == agg["n_ties"]           # its one margin is tier 1's: exactly the ties take the exact pipeline
+    else:
+        _status_words(agg, {-1: status}, tier0=())

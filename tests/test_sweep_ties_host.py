@@ -26,6 +26,20 @@ model disagrees with the C oracle -- measurements; the tests ask for one each:
   batched    5 (0)     48  48     9   0   4  18  31   4.3      batched   60 (1)     48  48    16   7   7   9  21   3.6
   batched  128 (2)     48  48    10   5   4  11  17   4.0      batched  100 (3)     48  48    14   5   4   9  24   3.2
   wide    4167 masked  48  48    14  14   5   4  21   8.2      wide    4295 masked  48  48    22  11   7   9  25  12.9
+Sub-problems that share the wavefronts of one batched launch (sweepties.BATCH_MIXED: 64 documents each, lanes 8 and 16), with
+  (f) the exact pipeline evaluated with the NEIGHBOURING group's K -- the sub-problem of the same KP -- at the site's own KP
+
+                    ties out     a   b   c   d   e   f     s                        ties out     a   b   c   d   e   f     s
+  mixed  100 (8)       24  24     7   3   3   3   9   1   4.7      mixed  128 (8)       24  24     6   2   3   6  14   2   4.8
+  mixed   60 (8)       24  24     8   3   3   5   8   2   6.8      mixed   64 (8)       24  24     8   4   5   5  12   3   5.6
+  mixed   96 (8)       24  24     5   2   2   5  15   -   3.6      mixed  100 (16)      24  24     4   5   4   7  13   1   3.8
+  mixed  128 (16)      24  24     7   6   3   7  10   2   3.3
+(96 has no neighbour of its KP.  (f) is a condition, not a measurement: with 6 .. 8 labels out of 100 few planted documents allow a
+topic of the one row the two sums treat differently, and the streams of BATCH_MIXED were chosen so that every paired state has one.
+Seconds on a machine on which batched 60 (1) took 8 s.)
+(All seconds of this docstring are what the FIRST test that asks for a state pays: sweepties.state is an lru_cache, and only that sharing
+keeps the other tests of a process cheap -- test_batched_wavefronts_from_their_order run on its own plants the four batched and the
+seven mixed states itself, 36 s on that machine.)
 (4167 and 4295: the largest K of five and of seven tiers, tests/layoutclasses.py tier_ks().  Their seconds are from a slower machine,
 on which wide 3000 took 7.6 s: 1.1 and 1.7 times that state's.)
 (s: seconds to generate the state on one core of the development machine; sweepties.state is cached, so the host and the GPU tests of a
@@ -41,8 +55,8 @@ import sweepties as st
 from neartie import _gap, _site_scores
 
 CASES = [("general", a) for a in st.GENERAL] + [("quad", (K,)) for K in st.QUAD] + [("sparse", a[:2]) for a in st.SPARSE] + \
-        [("wide", a) for a in st.WIDE] + [("batch", (i,)) for i in range(len(st.BATCH))]
-MAKE = dict(general=st.general_state, quad=st.quad_state, sparse=st.sparse_state, wide=st.wide_state, batch=st.batch_state)
+        [("wide", a) for a in st.WIDE] + [("batch", (i,)) for i in range(len(st.BATCH))] + [("mixed", (i,)) for i in range(len(st.MIXED_SUBS))]
+MAKE = dict(general=st.general_state, quad=st.quad_state, sparse=st.sparse_state, wide=st.wide_state, batch=st.batch_state, mixed=st.mixed_state)
 ids = ["%s-%s" % (f, "-".join(str(int(v)) for v in a)) for f, a in CASES]
 
 
@@ -96,7 +110,8 @@ def test_wavefronts_mix_planted_and_random_documents(family, args):
     s = MAKE[family](*args)
     lay = _lay(s)
     per_wave = s["per_wave"]
-    want = dict(general=max(64 // lay.G, 1), wide=1, quad=64 // (lay.G // 2), sparse=64 // st.sparse_lanes(args[-1]) if family == "sparse" else 0)[family]
+    want = dict(general=max(64 // lay.G, 1), wide=1, quad=64 // (lay.G // 2), sparse=64 // st.sparse_lanes(args[-1]) if family == "sparse" else 0,
+                mixed=64 // st.MIXED_SUBS[args[0]][1] if family == "mixed" else 0)[family]
     assert per_wave == want
     D = len(s["doc_off"]) - 1
     lens = np.diff(s["doc_off"])
@@ -108,6 +123,49 @@ def test_wavefronts_mix_planted_and_random_documents(family, args):
             assert s["planted"][docs].sum() == per_wave // 2 and len(set(lens[docs])) == 1         # ONE site index
     if per_wave == 1:
         assert list(s["planted"][:8:2]) == [True, False, True, False]
+
+
+def _waves(docs, per_wave):
+    return [docs[i:i + per_wave] for i in range(0, len(docs), per_wave)]
+
+
+def test_batched_wavefronts_from_their_order():
+    """The wavefronts of the two batched families as their launches compose them -- from ``order``, not from the states' own numbering.
+    batch: every sub-problem is its own lane class and Ensemble launches it longest document first (a stable sort), so a wavefront
+    holds ONE problem; the sort leaves whole blocks of the states together only where lengths agree, and what remains is asserted:
+    in every sub-problem of fewer than 64 lanes some wavefront holds planted and random documents of one length, and some holds
+    planted documents only (measured: 11 and 2 of 16 wavefronts at K = 5, 25 and 6 of 32 at K = 60, 31 and 32 of 64 at K = 128).
+    mixed (sweepties.mixed_order): EVERY wavefront holds min(P, 64 / lanes) >= 2 problems, no two neighbouring groups share one, it
+    holds planted and random documents, and the planted and random documents of its first half have one length (ONE site index)."""
+    for i, (K, _, hi) in enumerate(st.BATCH):
+        s = st.batch_state(i)
+        per_wave = 64 // st.sparse_lanes(hi - 1)
+        assert per_wave == s["per_wave"]
+        lens = np.diff(s["doc_off"])
+        order = np.argsort(-lens, kind="stable")                         # Ensemble.orders: longest first inside a lane class
+        both = only = 0
+        for docs in _waves(order, per_wave):
+            p = s["planted"][docs]
+            both += bool(p.any() and not p.all() and len(set(lens[docs])) == 1)
+            only += bool(p.all())
+        if per_wave == 1:                                                # 64 lanes a document: a wavefront IS one document
+            assert both == 0 and only == int(s["planted"].sum())
+        else:
+            assert both >= 1 and only >= 1, (i, both, only)
+    for g, (lanes, D, subs) in enumerate(st.BATCH_MIXED):
+        order = st.mixed_order(g)
+        per_wave, P = 64 // lanes, len(subs)
+        states = {i: st.mixed_state(i) for i in set(i for i, _ in order)}
+        assert len(states) == P and len(order) == P * D and len(order) % per_wave == 0
+        for wave in _waves(order, per_wave):
+            probs = [i for i, _ in wave]
+            assert len(set(probs)) == min(P, per_wave) >= 2 and all(a != b for a, b in zip(probs, probs[1:]))
+            planted = np.array([states[i]["planted"][d] for i, d in wave])
+            lens = np.array([np.diff(states[i]["doc_off"])[d] for i, d in wave])
+            half = per_wave // 2
+            assert planted[:half].sum() == half // 2 + half % 2 or planted[:half].sum() == half // 2, planted
+            assert planted[:half].any() and not planted[:half].all() and len(set(lens[:half])) == 1
+            assert planted[half:].all()
 
 
 @pytest.mark.parametrize("family,args", CASES, ids=ids)
@@ -126,8 +184,13 @@ def test_model_verdicts_and_discrimination(c_oracle, family, args):
     if family == "quad":                                                 # int32 rows take the standard order out of line: the same verdicts
         for i, r in enumerate(st.verdicts(s, quad=False)):
             assert r["sure"] != bool(r["planted"] and r["cls"].startswith("tie")) and (not r["sure"] or r["model"] == cs.z[i])
-    c = st.caught(s, quad=family == "quad")
+    other = st.mixed_neighbour(args[0]) if family == "mixed" else None
+    c = st.caught(s, quad=family == "quad", other_k=None if other is None else st.MIXED_SUBS[other][3])
     print(family, args, c)
+    if other is not None:
+        # (f) the exact pipeline with the NEIGHBOURING group's K at the site's own KP: a condition on the chosen pairings and streams,
+        # not a measurement; the same statement with the state's own K is the pipeline on every planted site
+        assert c["own"] == 0 and c["f"] >= 1, c
     assert c["ties"] == s["n_ties"] and c["outside"] == s["n_outside"]
     for model in "abcde":
         if model == "b" and _lay(s).K < 8:                               # numpy's sum of fewer than 8 terms is the sequential one
