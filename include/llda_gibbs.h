@@ -1114,6 +1114,95 @@ int llda_phistep_struct_bytes(void);
 int64_t llda_phi_step_scratch_bytes(int64_t V, int32_t K);
 int llda_phi_step(const llda_phistep_args *args, void *stream);
 
+/* The document model on sparse label sets (additive to ABI 22): llda_attribute and llda_credit_words for documents that carry a
+ * handful of the K labels.  A site gathers L_d entries of its word's row of phi_t where the dense entry points read K.
+ *   lab_off [D+1] int64, lab [NL] int32: the label sets, a CSR next to the sites: the labels of document d are
+ *   lab[lab_off[d]] .. lab[lab_off[d+1] - 1], strictly ascending, in [0, K).  L_d = lab_off[d+1] - lab_off[d].  NL = lab_off[D], the
+ *   caller states it.  lab_off must not descend (two documents never share a slot);
+ *   theta_s [NL] doubles: the loads, one per SLOT of lab; theta_out [NL] and credit [NL] live per slot too;
+ *   max_labels in 1 .. LLDA_SPARSE_MAX_LABELS: the longest list of the call.  The lane group is the smallest of 8, 16, 32 that is
+ *   >= max_labels, one value per call.
+ * A document is UNFIT when L_d > max_labels, when its offsets do not lie in [0, NL], when a label id is outside [0, K) or when its
+ * list is not strictly ascending (the kernel compares every id with its left neighbour's inside the group).  The label ids of an
+ * unfit document are never used as an index.  A document with L_d = 0 is fit: every site has p = 0.
+ * Arithmetic: that of llda_attribute word for word (every operation one IEEE float64 operation, rounded on its own; sum64,
+ * LLDA_ATTR_MIN_P, one division per site, g = (double)f * inv, num / den and the theta > 0 rule, ties by topic id) on the
+ * one-document problem with K' = L_d, theta' = the document's slots and phi_t'[w][j] = phi_t[w][lab[j]]:
+ *   site (w, f)  t[j] = theta_s[j] * phi_t[w][lab[j]];  p = sum64(t), over the L_d products in slot order.
+ * With the prefix 0 .. L_d - 1 as every label set and dense rows that are 0 elsewhere both entry points below give the bits of the
+ * dense entry points at full K (adding +0.0 to a sum that is never -0.0 is the identity).  For other label sets the two forms
+ * differ in the last bits of p: the dense sum64 pairs the products by topic id mod 64, this one by slot.
+ *
+ * llda_attribute_sparse: the fields of llda_attr_args with the label sets in place of theta and the row strides.
+ *   A fit document with L_d >= 1 gets, bit for bit, what llda_attribute gives on its one-document problem: theta_out, credit (per
+ *   slot), tok, bad, site_val of its sites, and site_idx with lab[j] where that problem has j.  A fit document with L_d = 0 writes
+ *   no slot; all its sites are bad.  An unfit document: every site adds f to bad, tok = 0, site_idx / site_val all -1 / 0.0; its
+ *   slots of theta_out keep theta_s and those of credit get +0.0 (offsets outside [0, NL]: no slot is written).
+ *   A document's outputs depend on its own inputs and on nothing else; tests/sparseref.py restates them.  D == 0 is a no-op.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a struct_bytes that is not the struct's; D < 0; V outside
+ * 1 .. 2^31 - 1; NL < 0; ld_phi < K; max_labels outside 1 .. LLDA_SPARSE_MAX_LABELS; iters < 0; alpha negative or NaN; top_m
+ * outside 0 .. 4; top_m > 0 with exactly one of site_idx / site_val NULL; with D > 0 a NULL doc_off, word, lab_off or phi_t, or
+ * (NL > 0) a NULL lab or theta_s; a misaligned pointer.  All before anything touches HIP. */
+#define LLDA_SPARSE_MAX_LABELS 32
+typedef struct llda_attr_sparse_args {
+    uint32_t struct_bytes;       /* sizeof(llda_attr_sparse_args)                                */
+    int32_t  K, max_labels, iters, top_m, reserved;
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S] or NULL                                            */
+    const int64_t *lab_off;      /* [dev] [D+1]                                                  */
+    const int32_t *lab;          /* [dev] [NL]                                                   */
+    const double  *theta_s;      /* [dev] [NL]                                                   */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    int64_t  D, V, NL, ld_phi;
+    double   alpha;
+    double  *theta_out;          /* [dev] [NL] or NULL                                           */
+    double  *credit;             /* [dev] [NL] or NULL                                           */
+    int32_t *site_idx;           /* [dev] [S][top_m] or NULL                                     */
+    double  *site_val;           /* [dev] [S][top_m] or NULL                                     */
+    int64_t *tok;                /* [dev] [D] or NULL                                            */
+    int64_t *bad;                /* [dev] [D] or NULL                                            */
+} llda_attr_sparse_args;
+int llda_attr_sparse_struct_bytes(void);
+int llda_attribute_sparse(const llda_attr_sparse_args *args, void *stream);
+
+/* llda_credit_words_sparse: llda_wcredit_args with the label sets in place of theta.  A site (d, f) of word v is OK when d is in
+ * [0, D) and document d is fit; then t[j] = theta_s[j] * phi_t[v][lab[j]] over the slots of d, p = sum64(t), and the site is GOOD
+ * when LLDA_ATTR_MIN_P <= p < inf.  A site that is not good adds f to bad[v] and nothing else.  A good site adds f to tok[v];
+ * inv = 1.0 / p; g = (double)f * inv; acc[lab[j]] = acc[lab[j]] + t[j] * g for its slots.
+ * The order of the sum is llda_credit_words': chunks of `chunk` consecutive sites of the word, a chunk added in ascending site
+ * order from +0.0, the chunk sums in ascending chunk order from +0.0.  credit_w is the same dense [V][ld_credit] rows; a column
+ * that no good site of the word reaches is +0.0.
+ * One wavefront per chunk (llda_credit_words' index and combine passes as they are), the chunk's K sums in LDS: 8 K bytes per
+ * wavefront, at most 61 504.  64 / G sites are worked at a time and commit to LDS one after the other in ascending site order.
+ * No floating-point atomics.  A word's outputs depend on its own sites, its row of phi_t, the label sets they name and chunk;
+ * tests/sparseref.py restates them.  scratch: llda_credit_words_sparse_scratch_bytes(V, S, K, chunk), the formula of
+ * llda_credit_words_scratch_bytes.  S == 0 still writes the zero rows; with every output NULL nothing is launched.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a struct_bytes that is not the struct's; D < 0; V outside
+ * 1 .. 2^31 - 1; S outside 0 .. LLDA_WCREDIT_MAX_SITES; NL < 0; ld_phi < K or ld_credit < K; chunk < 1; max_labels outside
+ * 1 .. LLDA_SPARSE_MAX_LABELS; with S > 0 a NULL word_off, site_doc, phi_t or scratch, a NULL lab_off (D > 0), a NULL lab or
+ * theta_s (NL > 0), or scratch_bytes below the query; a misaligned pointer.  All before anything touches HIP. */
+typedef struct llda_wcredit_sparse_args {
+    uint32_t struct_bytes;       /* sizeof(llda_wcredit_sparse_args)                             */
+    int32_t  K, chunk, max_labels;
+    const int64_t *word_off;     /* [dev] [V+1]                                                  */
+    const int32_t *site_doc;     /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S] or NULL                                            */
+    const int64_t *lab_off;      /* [dev] [D+1]                                                  */
+    const int32_t *lab;          /* [dev] [NL]                                                   */
+    const double  *theta_s;      /* [dev] [NL]                                                   */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    int64_t  D, V, S, NL, ld_phi, ld_credit;
+    double  *credit_w;           /* [dev] [V][ld_credit] or NULL                                 */
+    int64_t *tok;                /* [dev] [V] or NULL                                            */
+    int64_t *bad;                /* [dev] [V] or NULL                                            */
+    void    *scratch;            /* [dev] work space                                             */
+    int64_t  scratch_bytes;
+} llda_wcredit_sparse_args;
+int llda_wcredit_sparse_struct_bytes(void);
+int64_t llda_credit_words_sparse_scratch_bytes(int64_t V, int64_t S, int32_t K, int32_t chunk);
+int llda_credit_words_sparse(const llda_wcredit_sparse_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -289,7 +289,7 @@ class LabeledLDA(object):
             if bad & _native.READOUT_NO_LOAD:
                 raise ValueError('A word in dictionary has no z-value')
 
-    def fit_em(self, iters=50, theta_steps=1, start="counts", chunk=4096, trace_every=0):
+    def fit_em(self, iters=50, theta_steps=1, start="counts", chunk=4096, trace_every=0, sparse=False):
         """Fit ``ph_hat`` / ``th_hat`` by EM on the device, without random numbers (``emfit.fit``): ``iters`` passes
         of the theta M-step (``theta_steps`` steps of llda_attribute with alpha), the word-side E-step (llda_credit_words) and the
         phi M-step (llda_phi_step with beta).  start = "counts": from ``get_theta()`` / ``get_phi()`` of the current counts (the
@@ -300,6 +300,10 @@ class LabeledLDA(object):
         them.  z, the counts, the priors and the draw keys are not touched: a later ``run_training`` continues the chain as if this
         had not been called, and its first thinning read-out starts the running means afresh.  trace_every = n > 0: the data term
         sum f log p every n iterations.  Returns dict(iterations=iters, trace=[(iteration, loglik, tokens, bad), ...]).
+        sparse=True: the sparse-label form (``emfit.fit_sparse``) -- the label sets come from ``labs`` and the start
+        loads are the same theta at those labels; a site then costs len(labels) entries of phi, not K, on both sides of the
+        E-step.  At most 32 labels per document (ValueError beyond).  The sums pair their terms by slot, not by topic id, so the
+        estimates differ from the default's in their last bits (not at all where every label set is a prefix 0 .. L - 1).
         One device only: with several ranks it raises."""
         import torch
         from . import emfit, heldout
@@ -316,8 +320,16 @@ class LabeledLDA(object):
             ph0 = self._ph_hat.dev if self._ph_hat.dev is not None else torch.from_numpy(np.ascontiguousarray(self.ph_hat, dtype=np.float64))
             th0 = self._th_hat.dev if self._th_hat.dev is not None else torch.from_numpy(np.ascontiguousarray(self.th_hat, dtype=np.float64))
         doc_off, word, freq = csr_from_doc_tups(self.doc_tups)
-        r = emfit.fit(th0.to(dev), ph0.to(dev).t().contiguous(), doc_off, word, freq, float(self.alpha), float(self.beta), iters,
-                      theta_steps=theta_steps, chunk=chunk, trace_every=trace_every)
+        if sparse:
+            from . import attribution, docmodel
+            lab_off, lab = docmodel.label_csr(np.asarray(self.labs), K=self.K)
+            docmodel.label_sets(lab_off, lab, len(lab_off) - 1, self.K)     # (more than 32 labels in a document: ValueError, before any launch)
+            r = emfit.fit_sparse(attribution.gather_slots(th0.to(dev), lab_off, lab), ph0.to(dev).t().contiguous(), doc_off, word, freq,
+                                 lab_off, lab, float(self.alpha), float(self.beta), iters, theta_steps=theta_steps, chunk=chunk,
+                                 trace_every=trace_every)
+        else:
+            r = emfit.fit(th0.to(dev), ph0.to(dev).t().contiguous(), doc_off, word, freq, float(self.alpha), float(self.beta), iters,
+                          theta_steps=theta_steps, chunk=chunk, trace_every=trace_every)
         self._ph_hat.set(None)
         self._ph_hat.dev = r["phi_t"].t().contiguous()
         self._th_hat.set(None)
@@ -676,15 +688,28 @@ class LabeledLDA(object):
         return attribution.attribute(th0, self._phi_t_device() if phi_t is None else phi_t, doc_off, word, freq, iters=iters, alpha=float(self.alpha),
                                      top_m=top_m, want=want)
 
-    def fold_in_em(self, newdocs, iters=50, labels=None):
+    def fold_in_em(self, newdocs, iters=50, labels=None, sparse=False):
         """Fold unseen documents in by EM: (D, K) float64 loads after ``iters`` steps of theta_k = (credit_k + alpha) / sum from the
         uniform start over all K labels, or -- with ``labels``, one list of label strings per document -- over 'root' plus the
         document's labels.  No random numbers: the same document gets the same loads on every call.  A document with no
-        in-vocabulary word raises, as in ``run_test``.  The documents are independent: no collective."""
+        in-vocabulary word raises, as in ``run_test``.  The documents are independent: no collective.  sparse=True (with
+        ``labels``; at most 32 per document, root included): through ``attribution.attribute_sparse``, which reads a document's
+        own columns of phi only; the loads differ from the default's in their last bits."""
         tups = [self.dicti.doc2bow(x) for x in newdocs]
         start = self._em_start(tups, labels)
         if not tups:
             return start
+        if sparse:
+            import torch
+            from . import attribution, docmodel
+            if labels is None:
+                raise ValueError("sparse=True wants the label sets: labels must be given")
+            lab_off, lab = docmodel.label_csr(attribution.explain_label_cols(self.labelmap, len(tups), labels=labels), K=self.K)
+            doc_off, word, freq = csr_from_doc_tups(tups)
+            th0 = attribution.gather_slots(torch.from_numpy(start).to(self._attr_device()), lab_off, lab)
+            r = attribution.attribute_sparse(th0, self._phi_t_device(), doc_off, word, freq, lab_off, lab, iters=iters, alpha=float(self.alpha),
+                                             top_m=0, want=("theta",))
+            return attribution.scatter_slots(r["theta"], lab_off, lab, self.K).cpu().numpy()
         return self._fold_in_em_device(tups, start, iters)["theta"].cpu().numpy()
 
     def predict_em(self, newdocs, iters=50, n=5):
@@ -923,13 +948,13 @@ def prune_dict(docs, lower=0.1, upper=0.9):
     return dicti
 
 
-def train_it(traindata, it=30, s=3, al=0.001, be=0.001, l=0.05, u=0.95, em=0):
-    """em = n > 0: fit by ``fit_em(n)`` in place of ``run_training(it, s)``"""
+def train_it(traindata, it=30, s=3, al=0.001, be=0.001, l=0.05, u=0.95, em=0, em_sparse=False):
+    """em = n > 0: fit by ``fit_em(n)`` in place of ``run_training(it, s)``; em_sparse: its sparse-label form"""
     a, b, c = traindata
     dicti = prune_dict(a, lower=l, upper=u)
     llda = LabeledLDA(a, b, c, dicti, al, be)
     if em > 0:
-        llda.fit_em(em)
+        llda.fit_em(em, sparse=True) if em_sparse else llda.fit_em(em)
     else:
         llda.run_training(it, s)
     return llda

@@ -156,6 +156,22 @@ class LldaPhistepArgs(ctypes.Structure):
                 ("ld_out", _c_i64), ("beta", _c_d), ("scratch", _c_p), ("scratch_bytes", _c_i64)]
 
 
+class LldaAttrSparseArgs(ctypes.Structure):
+    """struct llda_attr_sparse_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("max_labels", _c_i32), ("iters", _c_i32), ("top_m", _c_i32), ("reserved", _c_i32),
+                ("doc_off", _c_p), ("word", _c_p), ("freq", _c_p), ("lab_off", _c_p), ("lab", _c_p), ("theta_s", _c_p), ("phi_t", _c_p),
+                ("D", _c_i64), ("V", _c_i64), ("NL", _c_i64), ("ld_phi", _c_i64), ("alpha", _c_d), ("theta_out", _c_p), ("credit", _c_p),
+                ("site_idx", _c_p), ("site_val", _c_p), ("tok", _c_p), ("bad", _c_p)]
+
+
+class LldaWcreditSparseArgs(ctypes.Structure):
+    """struct llda_wcredit_sparse_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("chunk", _c_i32), ("max_labels", _c_i32), ("word_off", _c_p), ("site_doc", _c_p),
+                ("freq", _c_p), ("lab_off", _c_p), ("lab", _c_p), ("theta_s", _c_p), ("phi_t", _c_p), ("D", _c_i64), ("V", _c_i64),
+                ("S", _c_i64), ("NL", _c_i64), ("ld_phi", _c_i64), ("ld_credit", _c_i64), ("credit_w", _c_p), ("tok", _c_p), ("bad", _c_p),
+                ("scratch", _c_p), ("scratch_bytes", _c_i64)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -169,7 +185,9 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_ecdf_struct_bytes", "llda_ecdf_scratch_bytes", "llda_ecdf_ranks",
            "llda_frex_struct_bytes", "llda_frex_scratch_bytes", "llda_frex_select",
            "llda_wcredit_struct_bytes", "llda_credit_words_scratch_bytes", "llda_credit_words",
-           "llda_phistep_struct_bytes", "llda_phi_step_scratch_bytes", "llda_phi_step")
+           "llda_phistep_struct_bytes", "llda_phi_step_scratch_bytes", "llda_phi_step",
+           "llda_attr_sparse_struct_bytes", "llda_attribute_sparse",
+           "llda_wcredit_sparse_struct_bytes", "llda_credit_words_sparse_scratch_bytes", "llda_credit_words_sparse")
 
 _LIB = None
 
@@ -303,6 +321,16 @@ def lib():
     L.llda_phi_step_scratch_bytes.argtypes = [_c_i64, _c_i32]
     L.llda_phi_step.restype = ctypes.c_int
     L.llda_phi_step.argtypes = [ctypes.POINTER(LldaPhistepArgs), _c_p]
+    L.llda_attr_sparse_struct_bytes.restype = ctypes.c_int
+    L.llda_attr_sparse_struct_bytes.argtypes = []
+    L.llda_attribute_sparse.restype = ctypes.c_int
+    L.llda_attribute_sparse.argtypes = [ctypes.POINTER(LldaAttrSparseArgs), _c_p]
+    L.llda_wcredit_sparse_struct_bytes.restype = ctypes.c_int
+    L.llda_wcredit_sparse_struct_bytes.argtypes = []
+    L.llda_credit_words_sparse_scratch_bytes.restype = _c_i64
+    L.llda_credit_words_sparse_scratch_bytes.argtypes = [_c_i64, _c_i64, _c_i32, _c_i32]
+    L.llda_credit_words_sparse.restype = ctypes.c_int
+    L.llda_credit_words_sparse.argtypes = [ctypes.POINTER(LldaWcreditSparseArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -324,7 +352,9 @@ def lib():
                                ("LldaScoredArgs", LldaScoredArgs, L.llda_scored_struct_bytes()),
                                ("LldaEcdfArgs", LldaEcdfArgs, L.llda_ecdf_struct_bytes()), ("LldaFrexArgs", LldaFrexArgs, L.llda_frex_struct_bytes()),
                                ("LldaWcreditArgs", LldaWcreditArgs, L.llda_wcredit_struct_bytes()),
-                               ("LldaPhistepArgs", LldaPhistepArgs, L.llda_phistep_struct_bytes())):
+                               ("LldaPhistepArgs", LldaPhistepArgs, L.llda_phistep_struct_bytes()),
+                               ("LldaAttrSparseArgs", LldaAttrSparseArgs, L.llda_attr_sparse_struct_bytes()),
+                               ("LldaWcreditSparseArgs", LldaWcreditSparseArgs, L.llda_wcredit_sparse_struct_bytes())):
         if size != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
@@ -683,6 +713,42 @@ def phi_step(cw, V, K, beta, out, scratch, *, ld=None, ld_out=None, den=None):
                         int(cw.stride(0) if ld is None else ld), int(out.stride(0) if ld_out is None else ld_out), float(beta),
                         _ptr(scratch), int(scratch.numel()))
     _launch(cw, lib().llda_phi_step, "llda_phi_step", ctypes.byref(a))
+
+
+SPARSE_MAX_LABELS = 32         # LLDA_SPARSE_MAX_LABELS: labels of a document in the sparse-label entry points at most
+
+
+def attribute_sparse(doc_off, word, freq, lab_off, lab, theta_s, phi_t, D, V, K, NL, max_labels, *, iters=0, alpha=0.0, top_m=0,
+                     ld_phi=None, theta_out=None, credit=None, site_idx=None, site_val=None, tok=None, bad=None):
+    """llda_attribute_sparse on the current torch stream: the CSR of the sites as ``attribute`` takes it; lab_off (int64 [D+1]) / lab
+    (int32 [NL]) the label sets, theta_s (float64 [NL]) the loads per slot; phi_t (V, ld_phi) float64; theta_out, credit (float64
+    [NL]), site_idx (S, top_m) int32, site_val (S, top_m) float64, tok, bad (int64 [D]) the outputs, each may be None."""
+    a = LldaAttrSparseArgs(ctypes.sizeof(LldaAttrSparseArgs), int(K), int(max_labels), int(iters), int(top_m), 0, _ptr(doc_off), _ptr(word),
+                           _ptr(freq), _ptr(lab_off), _ptr(lab), _ptr(theta_s), _ptr(phi_t), int(D), int(V), int(NL),
+                           int(phi_t.stride(0) if ld_phi is None else ld_phi), float(alpha), _ptr(theta_out), _ptr(credit), _ptr(site_idx),
+                           _ptr(site_val), _ptr(tok), _ptr(bad))
+    _launch(phi_t, lib().llda_attribute_sparse, "llda_attribute_sparse", ctypes.byref(a))
+
+
+def credit_words_sparse_scratch_bytes(V, S, K, chunk):
+    """llda_credit_words_sparse_scratch_bytes: bytes of work space llda_credit_words_sparse needs (host only)."""
+    r = int(lib().llda_credit_words_sparse_scratch_bytes(int(V), int(S), int(K), int(chunk)))
+    if r < 0:
+        check(r, "llda_credit_words_sparse_scratch_bytes(V=%d, S=%d, K=%d, chunk=%d)" % (V, S, K, chunk))
+    return r
+
+
+def credit_words_sparse(word_off, site_doc, freq, lab_off, lab, theta_s, phi_t, D, V, S, K, NL, max_labels, chunk, scratch, *, ld_phi=None,
+                        ld_credit=None, credit_w=None, tok=None, bad=None):
+    """llda_credit_words_sparse on the current torch stream: the word-major sites as ``credit_words`` takes them, the label sets and
+    the loads per slot as ``attribute_sparse`` does; credit_w (V, ld_credit) float64, tok, bad (int64 [V]) the outputs, each may be
+    None; scratch = a uint8 tensor of credit_words_sparse_scratch_bytes(V, S, K, chunk) bytes (None: S = 0)."""
+    a = LldaWcreditSparseArgs(ctypes.sizeof(LldaWcreditSparseArgs), int(K), int(chunk), int(max_labels), _ptr(word_off), _ptr(site_doc),
+                              _ptr(freq), _ptr(lab_off), _ptr(lab), _ptr(theta_s), _ptr(phi_t), int(D), int(V), int(S), int(NL),
+                              int(phi_t.stride(0) if ld_phi is None else ld_phi),
+                              int(K if credit_w is None else credit_w.stride(0)) if ld_credit is None else int(ld_credit),
+                              _ptr(credit_w), _ptr(tok), _ptr(bad), _ptr(scratch), 0 if scratch is None else int(scratch.numel()))
+    _launch(phi_t, lib().llda_credit_words_sparse, "llda_credit_words_sparse", ctypes.byref(a))
 
 
 LR_MAX_PARTICLES = 16          # LLDA_LR_MAX_PARTICLES

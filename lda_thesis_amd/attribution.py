@@ -10,8 +10,9 @@ M-step ``theta[k] = (credit[k] + alpha) / sum`` over the labels whose load is no
 numbers: the same document gets the same loads, always.  A label set is expressed by the start row: 0 outside the set
 (``uniform_start``), and a load that is 0 stays 0.
 
-The kernel reads the whole row of ``phi_t`` for every site even where ``theta`` is sparse.  A site whose p is below 2^-960 or not
-finite (or whose word is unknown) is attributed to nobody and counted in ``bad``.
+The kernel reads the whole row of ``phi_t`` for every site even where ``theta`` is sparse; ``attribute_sparse`` takes the label sets
+as a CSR and reads a document's own columns only.  A site whose p is below 2^-960 or not finite (or whose word is unknown) is
+attributed to nobody and counted in ``bad``.
 """
 import numpy as np
 
@@ -95,6 +96,81 @@ def attribute(theta_dev, phi_t_dev, doc_off, word, freq, iters=0, alpha=0.0, top
                       ld_out=K, ld_credit=K, theta_out=out.get("theta"), credit=out.get("credit"), site_idx=out.get("site_idx"),
                       site_val=out.get("site_val"), tok=out.get("tok"), bad=out.get("bad"))
     return out
+
+
+def _slots(x, NL, dev, name):
+    """x must be a float64 tensor of NL loads at least on dev; returned contiguous"""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float64 and x.dim() == 1 and x.device == dev and int(x.numel()) >= NL):
+        raise ValueError("%s must be a float64 tensor of %d loads (one per slot of lab) on phi_t's device" % (name, NL))
+    return x.contiguous() if NL else torch.zeros((1,), dtype=torch.float64, device=dev)
+
+
+def attribute_sparse(theta_s, phi_t_dev, doc_off, word, freq, lab_off, lab, iters=0, alpha=0.0, top_m=1, want=OUTPUTS):
+    """``attribute`` for documents that carry a few of the K labels (``llda_attribute_sparse``): the label sets are
+    the CSR lab_off (int64 [D+1]) / lab (ids ascending inside a document; ``docmodel.label_csr``), theta_s (float64 [NL], on the
+    device) holds the start loads per slot of lab.  A site reads len(labels) entries of its word's row of phi_t, not K.  Returns a dict
+    of device tensors, the ones ``want`` names: theta and credit float64 [NL] per slot, site_idx (label ids) / site_val (S, top_m),
+    tok, bad (int64 [D]).  ValueError on the host, before any launch, for label sets the kernel would call unfit."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    phi_t_dev = docmodel.matrix(phi_t_dev, "phi_t")
+    V, K = int(phi_t_dev.shape[0]), int(phi_t_dev.shape[1])
+    dev = phi_t_dev.device
+    iters, top_m, alpha = int(iters), int(top_m), float(alpha)
+    if iters < 0:
+        raise ValueError("iters must not be negative")
+    if not alpha >= 0.0:
+        raise ValueError("alpha must not be negative")
+    if not 0 <= top_m <= MAX_TOP:
+        raise ValueError("top_m must be in 0 .. %d" % MAX_TOP)
+    want = tuple(want)
+    if set(want) - set(OUTPUTS):
+        raise ValueError("want: unknown output %s" % sorted(set(want) - set(OUTPUTS)))
+    _, D, S = docmodel.check_offsets(doc_off)
+    off_h, lab_h, NL, max_labels = docmodel.label_sets(lab_off, lab, D, K)
+    theta_s = _slots(theta_s, NL, dev, "theta_s")
+    d_off, d_word, d_freq = docmodel.stage(dev, doc_off, word, freq, S, V)
+    d_loff, d_lab = docmodel.on_dev(off_h, torch.int64, dev), docmodel.on_dev(lab_h if NL else np.zeros(1), torch.int32, dev)
+    out = {}
+    for name in ("theta", "credit"):
+        if name in want:
+            out[name] = torch.empty((NL,), dtype=torch.float64, device=dev)
+    if "sites" in want and top_m > 0:
+        out["site_idx"] = torch.empty((S, top_m), dtype=torch.int32, device=dev)
+        out["site_val"] = torch.empty((S, top_m), dtype=torch.float64, device=dev)
+    for name in ("tok", "bad"):
+        if name in want:
+            out[name] = torch.empty((D,), dtype=torch.int64, device=dev)
+    _native.attribute_sparse(d_off, d_word, d_freq, d_loff, d_lab, theta_s, phi_t_dev, D, V, K, NL, max_labels, iters=iters, alpha=alpha,
+                             top_m=top_m if "site_idx" in out else 0, ld_phi=int(phi_t_dev.stride(0)) if V > 1 else K,
+                             theta_out=out.get("theta"), credit=out.get("credit"), site_idx=out.get("site_idx"),
+                             site_val=out.get("site_val"), tok=out.get("tok"), bad=out.get("bad"))
+    return out
+
+
+def scatter_slots(values, lab_off, lab, K):
+    """per-slot values (float64 [NL], device) -> the dense (D, K) rows, +0.0 outside the label sets; lab_off / lab host arrays"""
+    import torch
+    off_h = np.asarray(lab_off, dtype=np.int64)
+    D, NL = off_h.shape[0] - 1, int(off_h[-1]) if off_h.shape[0] else 0
+    out = torch.zeros((D, int(K)), dtype=torch.float64, device=values.device)
+    if NL:
+        rows = torch.from_numpy(np.repeat(np.arange(D, dtype=np.int64), np.diff(off_h))).to(values.device)
+        cols = torch.from_numpy(np.asarray(lab, dtype=np.int64)[:NL]).to(values.device)
+        out[rows, cols] = values[:NL]
+    return out
+
+
+def gather_slots(dense, lab_off, lab):
+    """the dense (D, K) rows (float64, device) -> their entries at the label sets, float64 [NL]"""
+    import torch
+    off_h = np.asarray(lab_off, dtype=np.int64)
+    D, NL = off_h.shape[0] - 1, int(off_h[-1])
+    rows = torch.from_numpy(np.repeat(np.arange(D, dtype=np.int64), np.diff(off_h))).to(dense.device)
+    cols = torch.from_numpy(np.asarray(lab, dtype=np.int64)[:NL]).to(dense.device)
+    return dense[rows, cols].contiguous()
 
 
 def spans(doc_off, site_idx, site_val):

@@ -199,9 +199,10 @@ __device__ __forceinline__ void group_docs(const DocModel &M, int64_t n_tiles, F
     }
 }
 
-// the sites 0 .. n_max of the group's document against the load th: site(site index, f, ok, live, p, t_k) in every lane
+// the sites 0 .. n_max of the group's document against the load th: site(site index, f, ok, live, p, t_k) in every lane.
+// col: the column of phi_t that the lane reads where g.mine -- its own number, or the label it holds (kernel_docsparse.hpp)
 template <int G, typename F>
-__device__ __forceinline__ void group_sites(const DocModel &M, const GroupDoc &g, double th, F &&site)
+__device__ __forceinline__ void group_sites_at(const DocModel &M, const GroupDoc &g, int col, double th, F &&site)
 {
     constexpr int U = 4;
     for (int64_t t = 0; t < g.n_max; t += U) {
@@ -214,7 +215,7 @@ __device__ __forceinline__ void group_sites(const DocModel &M, const GroupDoc &g
             const int32_t w = live ? M.word[g.b + t + u] : -1;
             f[u] = live ? (M.freq ? M.freq[g.b + t + u] : 1) : 0;
             ok[u] = word_ok(w, M.V);
-            v[u] = (ok[u] && g.mine) ? M.phi_t[(int64_t)w * M.ld_phi + g.gl] : 0.0;
+            v[u] = (ok[u] && g.mine) ? M.phi_t[(int64_t)w * M.ld_phi + col] : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -224,6 +225,12 @@ __device__ __forceinline__ void group_sites(const DocModel &M, const GroupDoc &g
             site(g.b + t + u, f[u], ok[u], t + u < g.n, doc_tree<G>(part), tk);
         }
     }
+}
+
+template <int G, typename F>
+__device__ __forceinline__ void group_sites(const DocModel &M, const GroupDoc &g, double th, F &&site)
+{
+    group_sites_at<G>(M, g, g.gl, th, site);
 }
 
 }  // namespace

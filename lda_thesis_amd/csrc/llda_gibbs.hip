@@ -58,6 +58,7 @@
 //                       llda_frex_select_kernel, llda_frex_merge_kernel   the n best words of every topic by two ranks (FREX): exact 96-bit compares
 //   kernel_emfit.hpp    llda_wcredit_index / _wave / _lds / _group / _combine kernels   the E-step's shares added up per word, in chunks of a word's sites
 //                       llda_phistep_block / _den / _div kernels   the phi M-step: column sums in a fixed order, one division per entry
+//   kernel_docsparse.hpp llda_attr_sparse_kernel, llda_wcredit_sparse_kernel   both on sparse label sets: a lane per label of the document, the word's sums in LDS
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -100,6 +101,7 @@
 #include "kernel_label.hpp"
 #include "kernel_ecdf.hpp"
 #include "kernel_emfit.hpp"
+#include "kernel_docsparse.hpp"
 
 namespace {
 
@@ -481,6 +483,42 @@ int launch_wcredit(const WCreditParams &P, int64_t chunks, hipStream_t st)
     if (rl) return rl;
     hipLaunchKernelGGL(llda_wcredit_lds_kernel, doc_grid(chunks, WCREDIT_LDS_MAX_BLOCKS), dim3(64), lds, st, P);
     return launched();
+}
+
+// the lane group of a sparse-label call: the smallest of 8, 16, 32 that holds max_labels
+constexpr int sparse_group(int max_labels) { return max_labels <= 8 ? 8 : max_labels <= 16 ? 16 : 32; }
+static_assert(sparse_group(1) == 8 && sparse_group(8) == 8 && sparse_group(9) == 16 && sparse_group(16) == 16 && sparse_group(17) == 32 &&
+              sparse_group(LLDA_SPARSE_MAX_LABELS) == 32, "sparse group seams");
+
+// wavefronts of a workgroup of llda_wcredit_sparse_kernel: as many of WCREDIT_WAVES as 32 KB of LDS hold, 8 K bytes each (K <= 1024: 4,
+// K <= 2048: 2, beyond: 1).  What is left of the CU's 160 KB goes to further workgroups.
+constexpr int wsparse_waves(int K) { return K <= 1024 ? WCREDIT_WAVES : K <= 2048 ? 2 : 1; }
+static_assert((size_t)wsparse_waves(LLDA_MAX_K) * LLDA_MAX_K * sizeof(double) <= 160 * 1024 && wsparse_waves(1024) * 1024 * 8 <= 32 * 1024 &&
+              wsparse_waves(2048) * 2048 * 8 <= 32 * 1024, "the sums of a workgroup fit the LDS of a CU");
+
+// llda_attribute_sparse: the lane group by max_labels (kernel_docsparse.hpp)
+template <bool SITES>
+int launch_attr_sparse(const AttrSparseParams &P, hipStream_t st)
+{
+    return visit_int<8, 16, 32>(sparse_group(P.sets.max_labels), [&](auto G) {
+        constexpr int docs = 64 * ATTR_WAVES / G.value;
+        const int64_t n_tiles = (P.D + docs - 1) / docs;
+        hipLaunchKernelGGL((llda_attr_sparse_kernel<G.value, SITES>), doc_grid(n_tiles), dim3(64 * ATTR_WAVES), 0, st, P, n_tiles);
+        return launched();
+    });
+}
+
+// llda_credit_words_sparse: the chunk kernel on at most `chunks` chunks
+int launch_wcredit_sparse(const WCreditSparseParams &P, int64_t chunks, hipStream_t st)
+{
+    const int waves = wsparse_waves(P.K);
+    const size_t lds = (size_t)waves * P.K * sizeof(double);
+    return visit_int<8, 16, 32>(sparse_group(P.sets.max_labels), [&](auto G) {
+        const int rl = allow_lds(llda_wcredit_sparse_kernel<G.value>, lds);
+        if (rl) return rl;
+        hipLaunchKernelGGL(llda_wcredit_sparse_kernel<G.value>, doc_grid((chunks + waves - 1) / waves), dim3(64 * waves), lds, st, P);
+        return launched();
+    });
 }
 
 // partial rows of llda_credit_words at most: a word with more than one chunk has more than `chunk` sites, so its chunks are fewer
@@ -1462,6 +1500,80 @@ int llda_credit_words(const llda_wcredit_args *a, void *stream)
         P.chunks_cap = wcredit_chunks_cap(a->V, a->S, a->chunk);
         hipLaunchKernelGGL(llda_wcredit_index_kernel, dim3(1), dim3(WCREDIT_INDEX_NT), 0, st, P);
         const int rc = launch_wcredit(P, P.chunks_cap, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(llda_wcredit_combine_kernel, doc_grid((a->V + WCREDIT_WAVES - 1) / WCREDIT_WAVES), dim3(64 * WCREDIT_WAVES), 0, st, P);
+    return launched();
+}
+
+int llda_attr_sparse_struct_bytes(void) { return (int)sizeof(llda_attr_sparse_args); }
+int llda_wcredit_sparse_struct_bytes(void) { return (int)sizeof(llda_wcredit_sparse_args); }
+
+int llda_attribute_sparse(const llda_attr_sparse_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_attr_sparse_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->NL < 0 || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if (a->max_labels < 1 || a->max_labels > LLDA_SPARSE_MAX_LABELS || a->iters < 0 || !(a->alpha >= 0.0) || a->top_m < 0 ||
+        a->top_m > LLDA_ATTR_MAX_TOP || (a->top_m > 0 && !a->site_idx != !a->site_val))
+        return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->lab_off || !a->phi_t || (a->NL > 0 && (!a->lab || !a->theta_s))) return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->lab_off, a->theta_s, a->phi_t, a->tok, a->bad) || misaligned(7, a->theta_out, a->credit, a->site_val) ||
+        misaligned(3, a->word, a->freq, a->lab, a->site_idx))
+        return LLDA_E_BAD_ARG;
+    AttrSparseParams P;
+    memset(&P, 0, sizeof P);
+    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.phi_t = a->phi_t;
+    P.D = a->D; P.V = a->V; P.ld_phi = a->ld_phi; P.K = a->K;
+    P.sets.lab_off = a->lab_off; P.sets.lab = a->lab; P.sets.theta_s = a->theta_s; P.sets.NL = a->NL; P.sets.max_labels = a->max_labels;
+    P.iters = a->iters; P.alpha = a->alpha;
+    P.theta_out = a->theta_out; P.credit = a->credit; P.tok = a->tok; P.bad = a->bad;
+    const bool sites = a->top_m > 0 && a->site_idx;                          // (top_m = 0 or no buffers: nothing in the site loop)
+    P.top_m = sites ? a->top_m : 0; P.site_idx = sites ? a->site_idx : nullptr; P.site_val = sites ? a->site_val : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    return sites ? launch_attr_sparse<true>(P, st) : launch_attr_sparse<false>(P, st);
+}
+
+int64_t llda_credit_words_sparse_scratch_bytes(int64_t V, int64_t S, int32_t K, int32_t chunk)
+{
+    return llda_credit_words_scratch_bytes(V, S, K, chunk);                  // (the same index tables and partial rows)
+}
+
+int llda_credit_words_sparse(const llda_wcredit_sparse_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_wcredit_sparse_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->S < 0 || a->S > LLDA_WCREDIT_MAX_SITES || a->NL < 0 || a->chunk < 1) return LLDA_E_BAD_ARG;
+    if (a->max_labels < 1 || a->max_labels > LLDA_SPARSE_MAX_LABELS || a->ld_phi < a->K || a->ld_credit < a->K) return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / a->ld_phi || a->V > INT64_MAX / a->ld_credit) return LLDA_E_BAD_ARG;
+    if (a->S > 0 && (!a->word_off || !a->site_doc || !a->phi_t || !a->scratch || (a->D > 0 && !a->lab_off) || (a->NL > 0 && (!a->lab || !a->theta_s))))
+        return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->word_off, a->lab_off, a->theta_s, a->phi_t, a->credit_w, a->tok) || misaligned(7, a->bad) || misaligned(7, a->scratch) ||
+        misaligned(3, a->site_doc, a->freq, a->lab))
+        return LLDA_E_BAD_ARG;
+    const int64_t need = llda_credit_words_sparse_scratch_bytes(a->V, a->S, a->K, a->chunk);
+    if (a->S > 0 && (need < 0 || a->scratch_bytes < need)) return LLDA_E_BAD_ARG;
+    if (!a->credit_w && !a->tok && !a->bad) return LLDA_OK;
+    WCreditSparseParams P;
+    memset(&P, 0, sizeof P);
+    P.word = a->site_doc; P.freq = a->freq; P.K = a->K; P.V = a->D;          // (the "words" of the sites are document ids)
+    P.sets.lab_off = a->lab_off; P.sets.lab = a->lab; P.sets.theta_s = a->theta_s; P.sets.NL = a->NL; P.sets.max_labels = a->max_labels;
+    P.word_off = a->word_off; P.wphi = a->phi_t; P.n_words = a->V; P.ld_wphi = a->ld_phi; P.ld_credit = a->ld_credit;
+    P.S = a->S; P.chunk = a->chunk; P.rows_cap = wcredit_rows(a->S, a->chunk);
+    P.credit_w = a->credit_w; P.tok = a->tok; P.bad = a->bad;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->S > 0) {
+        P.cfirst = static_cast<int64_t *>(a->scratch);
+        P.pfirst = P.cfirst + (a->V + 1);
+        P.ptok = P.pfirst + (a->V + 1);
+        P.pbad = P.ptok + P.rows_cap;
+        P.part = reinterpret_cast<double *>(P.pbad + P.rows_cap);
+        P.cword = reinterpret_cast<int32_t *>(P.part + P.rows_cap * a->K);
+        P.chunks_cap = wcredit_chunks_cap(a->V, a->S, a->chunk);
+        hipLaunchKernelGGL(llda_wcredit_index_kernel, dim3(1), dim3(WCREDIT_INDEX_NT), 0, st, P);
+        const int rc = launch_wcredit_sparse(P, P.chunks_cap, st);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(llda_wcredit_combine_kernel, doc_grid((a->V + WCREDIT_WAVES - 1) / WCREDIT_WAVES), dim3(64 * WCREDIT_WAVES), 0, st, P);

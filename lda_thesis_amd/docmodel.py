@@ -42,6 +42,49 @@ def matrices(theta, phi_t):
     return theta, phi_t, D, int(phi_t.shape[0]), K
 
 
+def label_csr(labs, K=None):
+    """Host only.  The label sets of D documents as a CSR: (lab_off int64 [D+1], lab int32 [NL]), every document's ids ascending.
+    ``labs`` is a (D, K) array whose non-zero entries are the labels, or one sequence of label ids per document (any order; K
+    given: the ids must be in [0, K)).  ValueError for an id out of range or a label named twice."""
+    if isinstance(labs, np.ndarray) and labs.ndim == 2:
+        if K is not None and labs.shape[1] != int(K):
+            raise ValueError("labs has %d columns, K is %d" % (labs.shape[1], int(K)))
+        rows, cols = np.nonzero(labs)                                       # (row-major: ascending within a document)
+        lab_off = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=labs.shape[0]))]).astype(np.int64)
+        return lab_off, cols.astype(np.int32)
+    lists = [np.sort(np.asarray(list(x), dtype=np.int64)) for x in labs]
+    for d, c in enumerate(lists):
+        if c.size and (c[0] < 0 or c[-1] >= (2 ** 31 if K is None else int(K))):
+            raise ValueError("document %d: a label id is outside 0 .. %s" % (d, "2^31 - 1" if K is None else int(K) - 1))
+        if np.any(np.diff(c) == 0):
+            raise ValueError("document %d: a label is named twice" % d)
+    lab_off = np.concatenate([[0], np.cumsum([c.size for c in lists])]).astype(np.int64)
+    return lab_off, (np.concatenate(lists) if lists else np.zeros(0)).astype(np.int32)
+
+
+def label_sets(lab_off, lab, D, K, limit=_native.SPARSE_MAX_LABELS):
+    """Host check of a label CSR (sequences, numpy arrays or tensors) before a sparse-label launch -> (off_h, lab_h, NL, max_labels):
+    D + 1 ascending offsets from 0, NL ids in [0, K) that ascend strictly inside every document, at most ``limit`` per document.
+    max_labels is the longest list, 1 at least."""
+    off_h, _, NL = check_offsets(lab_off, D)
+    lab_h = lab.cpu().numpy() if hasattr(lab, "cpu") else np.asarray(lab)
+    if D and int(off_h[0]) != 0:
+        raise ValueError("lab_off must start at 0")
+    if lab_h.ndim != 1 or lab_h.shape[0] < NL:
+        raise ValueError("lab holds %d label ids, lab_off asks for %d" % (lab_h.shape[0] if lab_h.ndim == 1 else -1, NL))
+    lab_h = lab_h[:NL].astype(np.int64)
+    if NL and (int(lab_h.min()) < 0 or int(lab_h.max()) >= K):
+        raise ValueError("label ids must be in [0, K)")
+    inner = np.ones(max(NL - 1, 0), dtype=bool)
+    inner[off_h[1:-1][(off_h[1:-1] > 0) & (off_h[1:-1] < NL)] - 1] = False  # (the step from one document's list to the next)
+    if NL > 1 and np.any((np.diff(lab_h) <= 0) & inner):
+        raise ValueError("the label ids of a document must ascend strictly")
+    longest = int(np.diff(off_h).max()) if D else 0
+    if longest > limit:
+        raise ValueError("a document has %d labels: the sparse-label form takes %d at most" % (longest, limit))
+    return off_h, lab_h.astype(np.int32), NL, max(longest, 1)
+
+
 def on_dev(a, dt, dev):
     """a (integers: numpy array, sequence or tensor) as a contiguous tensor of dtype dt on dev"""
     import torch

@@ -87,6 +87,45 @@ def credit_words(theta, phi_t, word_off, site_doc, freq, chunk=DEFAULT_CHUNK, wa
     return out
 
 
+def credit_words_sparse(theta_s, phi_t, word_off, site_doc, freq, lab_off, lab, chunk=DEFAULT_CHUNK, want=("credit", "tok", "bad")):
+    """``credit_words`` for documents that carry a few of the K labels (``llda_credit_words_sparse``): the label sets
+    are the CSR lab_off (int64 [D+1]) / lab (``docmodel.label_csr``), theta_s (float64 [NL], on the device) the loads per slot.
+    Returns the same dict: credit (V, K) float64 dense rows, tok, bad (int64 [V]).  ValueError on the host, before any launch, for
+    shapes that do not fit and for label sets the kernel would call unfit."""
+    import torch
+    from . import attribution
+    _native.lib()
+    _native.require_device()
+    phi_t = docmodel.matrix(phi_t, "phi_t")
+    V, K = int(phi_t.shape[0]), int(phi_t.shape[1])
+    dev = phi_t.device
+    chunk = _check_chunk(chunk)
+    want = tuple(want)
+    if set(want) - {"credit", "tok", "bad"}:
+        raise ValueError("want: unknown output %s" % sorted(set(want) - {"credit", "tok", "bad"}))
+    _, D, _ = docmodel.check_offsets(lab_off)
+    off_h, lab_h, NL, max_labels = docmodel.label_sets(lab_off, lab, D, K)
+    theta_s = attribution._slots(theta_s, NL, dev, "theta_s")
+    _, _, S = docmodel.check_offsets(word_off, V)
+    d_off, d_doc, d_freq = docmodel.stage(dev, word_off, site_doc, freq, S, unit="sites")
+    if S and D and (int(d_doc[:S].min()) < 0 or int(d_doc[:S].max()) >= D):
+        raise ValueError("document ids must be in [0, D)")
+    if S and not D:
+        raise ValueError("there are sites and no document")
+    d_loff, d_lab = docmodel.on_dev(off_h, torch.int64, dev), docmodel.on_dev(lab_h if NL else np.zeros(1), torch.int32, dev)
+    out = {}
+    if "credit" in want:
+        out["credit"] = torch.empty((V, K), dtype=torch.float64, device=dev)
+    for name in ("tok", "bad"):
+        if name in want:
+            out[name] = torch.empty((V,), dtype=torch.int64, device=dev)
+    scratch = torch.empty((_native.credit_words_sparse_scratch_bytes(V, S, K, chunk),), dtype=torch.uint8, device=dev) if S else None
+    _native.credit_words_sparse(d_off, d_doc, d_freq, d_loff, d_lab, theta_s, phi_t, D, V, S, K, NL, max_labels, chunk, scratch,
+                                ld_phi=int(phi_t.stride(0)) if V > 1 else K, ld_credit=K, credit_w=out.get("credit"), tok=out.get("tok"),
+                                bad=out.get("bad"))
+    return out
+
+
 def phi_step(cw, beta, out=None, want_den=False):
     """The phi M-step: cw (V, K) float64 on the device, the word credit -> phi_t (V, K) = (cw + beta) / (column sums + V beta).
     ``out``: where to (a (V, K) float64 tensor on the same device; it may be cw itself); None: a new tensor.  want_den: return
@@ -153,3 +192,50 @@ def fit(theta0, phi_t0, doc_off, word, freq, alpha, beta, iters, theta_steps=1, 
             r = heldout.perplexity_from(*heldout.loglik(theta, phi_t, d_off, d_word, d_freq))
             trace.append((it, r["loglik"], r["tokens"], r["bad"]))
     return dict(theta=theta, phi_t=phi_t, iterations=iters, trace=trace)
+
+
+def fit_sparse(theta_s0, phi_t0, doc_off, word, freq, lab_off, lab, alpha, beta, iters, theta_steps=1, chunk=DEFAULT_CHUNK, trace_every=0):
+    """``fit`` for documents that carry a few of the K labels: the same loop on ``llda_attribute_sparse`` and
+    ``llda_credit_words_sparse`` plus the unchanged ``phi_step``.  theta_s0 (float64 [NL], on the device) holds the start loads per
+    slot of the label CSR lab_off / lab (``docmodel.label_csr``); phi_t0 is (V, K).  A site costs len(labels) gathered entries on
+    either side, whatever K is.  The trace is ``heldout.loglik`` on the loads scattered to (D, K).  Returns dict(theta_s [NL],
+    phi_t (V, K), theta (D, K): theta_s scattered, +0.0 outside the label sets; iterations, trace)."""
+    import torch
+    from . import attribution, heldout
+    _native.lib()
+    _native.require_device()
+    phi_t = docmodel.matrix(phi_t0, "phi_t")
+    V, K = int(phi_t.shape[0]), int(phi_t.shape[1])
+    dev = phi_t.device
+    iters, theta_steps, trace_every, chunk = int(iters), int(theta_steps), int(trace_every), _check_chunk(chunk)
+    alpha, beta = float(alpha), float(beta)
+    if iters < 0 or theta_steps < 1 or trace_every < 0:
+        raise ValueError("iters >= 0, theta_steps >= 1 and trace_every >= 0 are wanted")
+    if not alpha >= 0.0:
+        raise ValueError("alpha must not be negative")
+    if not (beta > 0.0 and beta < float("inf")):
+        raise ValueError("beta must be a finite number above 0")
+    _, D, S = docmodel.check_offsets(doc_off)
+    off_h, lab_h, NL, max_labels = docmodel.label_sets(lab_off, lab, D, K)
+    theta_s = attribution._slots(theta_s0, NL, dev, "theta_s0").clone()
+    d_off, d_word, d_freq = docmodel.stage(dev, doc_off, word, freq, S, V)
+    word_off, site_doc, w_freq, _ = word_major(d_off, d_word, d_freq, V, dev)
+    d_loff, d_lab = docmodel.on_dev(off_h, torch.int64, dev), docmodel.on_dev(lab_h if NL else np.zeros(1), torch.int32, dev)
+    phi_t = phi_t.contiguous().clone()                                              # (row stride K from here on)
+    spare = torch.empty_like(theta_s)
+    cw = torch.empty((V, K), dtype=torch.float64, device=dev)
+    scratch = torch.empty((max(_native.credit_words_sparse_scratch_bytes(V, S, K, chunk), _native.phi_step_scratch_bytes(V, K)),),
+                          dtype=torch.uint8, device=dev)
+    trace = []
+    for it in range(1, iters + 1):
+        if D:
+            _native.attribute_sparse(d_off, d_word, d_freq, d_loff, d_lab, theta_s, phi_t, D, V, K, NL, max_labels, iters=theta_steps,
+                                     alpha=alpha, top_m=0, ld_phi=K, theta_out=spare)
+            theta_s, spare = spare, theta_s
+        _native.credit_words_sparse(word_off, site_doc, w_freq, d_loff, d_lab, theta_s, phi_t, D, V, S, K, NL, max_labels, chunk,
+                                    scratch if S else None, ld_phi=K, ld_credit=K, credit_w=cw)
+        _native.phi_step(cw, V, K, beta, phi_t, scratch, ld=K, ld_out=K)
+        if trace_every and it % trace_every == 0:
+            r = heldout.perplexity_from(*heldout.loglik(attribution.scatter_slots(theta_s, off_h, lab_h, K), phi_t, d_off, d_word, d_freq))
+            trace.append((it, r["loglik"], r["tokens"], r["bad"]))
+    return dict(theta_s=theta_s[:NL], phi_t=phi_t, theta=attribution.scatter_slots(theta_s, off_h, lab_h, K), iterations=iters, trace=trace)

@@ -58,6 +58,9 @@ def build_parser():
     p.add_option("--em-train", dest="em_train", type="int", default=0, metavar="ITERS",
                  help="fit the model by ITERS passes of deterministic EM (llda_attribute, llda_credit_words, llda_phi_step) in place "
                       "of the Gibbs sweeps of -i / -s, which then only set the fold-in of the test documents")
+    p.add_option("--em-sparse", dest="em_sparse", action="store_true", default=False,
+                 help="with --em-train: the sparse-label form of the EM fit (llda_attribute_sparse, llda_credit_words_sparse): a site "
+                      "reads its document's own labels of phi, not all K; at most 32 labels per document")
     p.add_option("--explain", dest="explain", type="int", default=0, metavar="N",
                  help="after the report: for the first N test documents the suggested labels with the five most-credited words "
                       "of each (llda_attribute)")
@@ -292,7 +295,8 @@ def main(argv=None):
         opt.thinning = opt.it
     train, test = split_data(f=opt.file, d=opt.lvl)
     print("Starting training...")
-    model = train_it(train, it=opt.it, s=opt.thinning, al=opt.alpha, be=opt.beta, l=opt.lower, u=opt.upper, em=opt.em_train)
+    model = train_it(train, it=opt.it, s=opt.thinning, al=opt.alpha, be=opt.beta, l=opt.lower, u=opt.upper, em=opt.em_train,
+                     em_sparse=opt.em_sparse)
     print("Testing test data, this may take a while...")
     th, _ = test_it(model, test, it=opt.it, thinning=opt.thinning)
     th = np.array(th)
