@@ -1203,6 +1203,83 @@ int llda_wcredit_sparse_struct_bytes(void);
 int64_t llda_credit_words_sparse_scratch_bytes(int64_t V, int64_t S, int32_t K, int32_t chunk);
 int llda_credit_words_sparse(const llda_wcredit_sparse_args *args, void *stream);
 
+/* llda_heldout_loglik_sparse (additive to ABI 22): llda_heldout_args with the label sets (lab_off, lab, theta_s,
+ * NL, max_labels as above) in place of theta and ld_theta.
+ * Arithmetic: llda_heldout_loglik's word for word on the document's compacted problem, K' = L_d, theta' = the document's slots,
+ * phi_t'[w][j] = phi_t[w][lab[j]]:
+ *   site (w, f)  p = sum64 of the L_d products theta_s[j] * phi_t[w][lab[j]] in slot order; then frexp(p), p^f by right-to-left
+ *                binary exponentiation, the document's pair product and the good / bad rule of llda_heldout_loglik, unchanged.
+ * A fit document with L_d = 0 has p = 0 at every site: all its sites are bad.  An UNFIT document: every site adds f to bad, tok = 0,
+ * the pair stays (0.5, 1), and none of its label ids is used as an index.  mant, expo, tok, bad [D]: each may be NULL.
+ * With the prefix 0 .. L_d - 1 as every label set it gives the bits of llda_heldout_loglik on the scattered theta (+0.0 elsewhere);
+ * for other sets the two differ in the last bits of p (sum64 pairs by slot here, by topic id mod 64 there).
+ * G = the smallest of 8, 16, 32 >= max_labels lanes per document, 64 / G documents per wavefront; a site gathers L_d doubles.
+ * A document's outputs depend on its own inputs only; tests/sparseheldref.py restates them.  D == 0 is a no-op.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a struct_bytes that is not the struct's; D < 0; V outside
+ * 1 .. 2^31 - 1; NL < 0; ld_phi < K; max_labels outside 1 .. LLDA_SPARSE_MAX_LABELS; with D > 0 a NULL doc_off, word, lab_off or
+ * phi_t, or (NL > 0) a NULL lab or theta_s; a misaligned pointer.  All before anything touches HIP. */
+typedef struct llda_heldout_sparse_args {
+    uint32_t struct_bytes;       /* sizeof(llda_heldout_sparse_args)                             */
+    int32_t  K, max_labels, reserved;
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S] or NULL                                            */
+    const int64_t *lab_off;      /* [dev] [D+1]                                                  */
+    const int32_t *lab;          /* [dev] [NL]                                                   */
+    const double  *theta_s;      /* [dev] [NL]                                                   */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    int64_t  D, V, NL, ld_phi;
+    double  *mant;               /* [dev] [D] or NULL                                            */
+    int64_t *expo;               /* [dev] [D] or NULL                                            */
+    int64_t *tok;                /* [dev] [D] or NULL                                            */
+    int64_t *bad;                /* [dev] [D] or NULL                                            */
+} llda_heldout_sparse_args;
+int llda_heldout_sparse_struct_bytes(void);
+int llda_heldout_loglik_sparse(const llda_heldout_sparse_args *args, void *stream);
+
+/* llda_left_to_right_sparse (additive to ABI 22): llda_leftright_args with the label sets (lab_off, lab, NL,
+ * max_labels as above; no loads) in place of allowed and ld_allowed, for every K in 1 .. LLDA_MAX_K: the label-conditioned document
+ * likelihood p(w_d | labels_d) at the cost of L_d gathered doubles per draw, whatever K is.
+ * Arithmetic: the text of llda_left_to_right on the document's compacted problem -- K' = L_d, phi_t'[w][j] = phi_t[w][lab[j]],
+ * every topic allowed, A = L_d -- with the same doc_ids, stream_id + r, seed and u(n, r, m).  Compacted topic j sits in lane j,
+ * slot 0, so draw64 and sum64 are those of K' <= 32 <= 64 topics.  The kernel works them on the G = 8, 16 or 32 >= max_labels lanes
+ * of a group, which gives the same bits: the lanes >= L_d hold +0.0 and x is never -0.0, so (i) the Hillis-Steele steps d >= G
+ * leave the prefixes of the lanes < G as they are, and X[63] = X[G-1] + (a sum of +0.0s) = X[G-1]; (ii) the steps s >= G of sum64's
+ * tree add +0.0.  The assignment a position holds is the SLOT j.  With the prefix 0 .. L_d - 1 as the label set the outputs are
+ * also those of llda_left_to_right at full K with the prefix as the allowed row (K <= 1024).
+ * An UNFIT document: every token is bad, tok = 0, the pair stays (0.5, 1) and no label id is used as an index.  L_d = 0 (fit):
+ * A = 0, every pred is NaN, every token is bad.  max_doc_tokens and status bit 0 as in llda_left_to_right (such a document gets
+ * (0.5, 1, 0, 0)).  mant, expo, tok, bad are required.
+ * One workgroup per document; particle r is the lane group r of the workgroup (64 / G particles per wavefront, ceil(R G / 64)
+ * wavefronts); one count per lane; the words (32 bits) and the assignments (8 bits per particle) in LDS, sized by max_doc_tokens.
+ * A document's outputs depend on its own tokens, its id, its label list and the scalars only; tests/sparseheldref.py restates them.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a struct_bytes that is not the struct's; D < 0; V outside
+ * 1 .. 2^31 - 1; NL < 0; ld_phi < K; max_labels outside 1 .. LLDA_SPARSE_MAX_LABELS; R outside 1 .. LLDA_LR_MAX_PARTICLES; alpha
+ * not a finite number > 0; max_doc_tokens outside 1 .. LLDA_LR_MAX_TOKENS; with D > 0 a NULL doc_off, word, lab_off, phi_t, mant,
+ * expo, tok or bad, or (NL > 0) a NULL lab; a misaligned pointer.  All before anything touches HIP. */
+typedef struct llda_leftright_sparse_args {
+    uint32_t struct_bytes;       /* sizeof(llda_leftright_sparse_args)                           */
+    int32_t  K, R, max_doc_tokens;
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    const int64_t *lab_off;      /* [dev] [D+1]                                                  */
+    const int32_t *lab;          /* [dev] [NL]                                                   */
+    const int64_t *doc_ids;      /* [dev] [D] or NULL                                            */
+    int64_t  D, V, ld_phi, NL, doc_base;
+    double   alpha;
+    uint64_t seed;
+    uint32_t stream_id;
+    int32_t  max_labels;
+    double  *mant;               /* [dev] [D]                                                    */
+    int64_t *expo;               /* [dev] [D]                                                    */
+    int64_t *tok;                /* [dev] [D]                                                    */
+    int64_t *bad;                /* [dev] [D]                                                    */
+    int32_t *status;             /* [dev] [1] or NULL                                            */
+} llda_leftright_sparse_args;
+int llda_leftright_sparse_struct_bytes(void);
+int llda_left_to_right_sparse(const llda_leftright_sparse_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -289,7 +289,7 @@ class LabeledLDA(object):
             if bad & _native.READOUT_NO_LOAD:
                 raise ValueError('A word in dictionary has no z-value')
 
-    def fit_em(self, iters=50, theta_steps=1, start="counts", chunk=4096, trace_every=0, sparse=False):
+    def fit_em(self, iters=50, theta_steps=1, start="counts", chunk=4096, trace_every=0, sparse=False, sparse_trace=False):
         """Fit ``ph_hat`` / ``th_hat`` by EM on the device, without random numbers (``emfit.fit``): ``iters`` passes
         of the theta M-step (``theta_steps`` steps of llda_attribute with alpha), the word-side E-step (llda_credit_words) and the
         phi M-step (llda_phi_step with beta).  start = "counts": from ``get_theta()`` / ``get_phi()`` of the current counts (the
@@ -304,6 +304,7 @@ class LabeledLDA(object):
         loads are the same theta at those labels; a site then costs len(labels) entries of phi, not K, on both sides of the
         E-step.  At most 32 labels per document (ValueError beyond).  The sums pair their terms by slot, not by topic id, so the
         estimates differ from the default's in their last bits (not at all where every label set is a prefix 0 .. L - 1).
+        sparse_trace=True (with sparse): the trace is scored on the slots too (llda_heldout_loglik_sparse), not on a (D, K) matrix.
         One device only: with several ranks it raises."""
         import torch
         from . import emfit, heldout
@@ -311,6 +312,8 @@ class LabeledLDA(object):
             raise ValueError("fit_em runs on one device only: it was called with %d ranks" % _world_size())
         if start not in ("counts", "ph_hat"):
             raise ValueError("start must be 'counts' or 'ph_hat'")
+        if sparse_trace and not sparse:
+            raise ValueError("sparse_trace=True goes with sparse=True")
         sm = self._sampler
         sm.check_status()
         dev = sm.device
@@ -326,7 +329,7 @@ class LabeledLDA(object):
             docmodel.label_sets(lab_off, lab, len(lab_off) - 1, self.K)     # (more than 32 labels in a document: ValueError, before any launch)
             r = emfit.fit_sparse(attribution.gather_slots(th0.to(dev), lab_off, lab), ph0.to(dev).t().contiguous(), doc_off, word, freq,
                                  lab_off, lab, float(self.alpha), float(self.beta), iters, theta_steps=theta_steps, chunk=chunk,
-                                 trace_every=trace_every)
+                                 trace_every=trace_every, sparse_trace=bool(sparse_trace))
         else:
             r = emfit.fit(th0.to(dev), ph0.to(dev).t().contiguous(), doc_off, word, freq, float(self.alpha), float(self.beta), iters,
                           theta_steps=theta_steps, chunk=chunk, trace_every=trace_every)
@@ -593,8 +596,59 @@ class LabeledLDA(object):
         r = heldout.perplexity_from(*heldout.loglik(theta, ph_dev.t().contiguous(), doc_off, word, freq, weighted=weighted))
         return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped)
 
+    def heldout_perplexity_em(self, newdocs, iters=50, labels=None, sparse=False, weighted=True, scored_docs=None):
+        """Document completion without random numbers, the deterministic sibling of ``heldout_perplexity``: the same split
+        (``heldout.completion_split``, or ``scored_docs``) and skip rules, the observed halves folded in by ``iters`` EM steps as
+        ``fold_in_em`` does (``labels``: over 'root' plus the document's own labels; sparse=True, with ``labels``: through the
+        sparse-label kernels), the loads smoothed with the observed tokens W_d and the scored halves scored on the device.
+        Without labels theta = (W_d th + alpha) / (W_d + K alpha); with labels the label count L_d (root included) takes K's place
+        on the allowed columns and theta is 0 elsewhere.  sparse=True keeps the loads per slot from the fold-in to the score
+        (llda_attribute_sparse, llda_heldout_loglik_sparse): no (D, K) matrix is formed, at most 32 labels per document, and the
+        figures equal the default's bit for bit where every label set is a prefix 0 .. L - 1.
+        Returns dict(perplexity, loglik, tokens, documents, skipped).  The same call gives the same bits every time."""
+        import torch
+        from . import attribution, docmodel, heldout
+        if sparse and labels is None:
+            raise ValueError("sparse=True wants the label sets: labels must be given")
+        if labels is not None and len(labels) != len(newdocs):
+            raise ValueError("labels must hold one list per document of newdocs")
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        if scored_docs is None:
+            observed, scored = heldout.completion_split(tups)
+        else:
+            if len(scored_docs) != len(tups):
+                raise ValueError("scored_docs must hold one token list per document of newdocs")
+            observed, scored = tups, [self.dicti.doc2bow(x) for x in scored_docs]
+        keep = [d for d, t in enumerate(observed) if t]
+        skipped = len(tups) - len(keep)
+        if not keep:
+            return dict(perplexity=float("nan"), loglik=0.0, tokens=0, documents=0, skipped=skipped)
+        observed, scored = [observed[d] for d in keep], [scored[d] for d in keep]
+        cols = None if labels is None else attribution.explain_label_cols(self.labelmap, len(keep), labels=[labels[d] for d in keep])
+        start = attribution.uniform_start(cols, len(keep), self.K)
+        dev = self._attr_device()
+        phi_t = self._phi_t_device()
+        alpha = float(self.alpha)
+        w_obs = torch.from_numpy(heldout.observed_tokens(observed)).to(dev)
+        o_off, o_word, o_freq = csr_from_doc_tups(observed)
+        s_off, s_word, s_freq = csr_from_doc_tups(scored)
+        if sparse:
+            lab_off, lab = docmodel.label_csr(cols, K=self.K)
+            th0 = attribution.gather_slots(torch.from_numpy(start).to(dev), lab_off, lab)
+            th = attribution.attribute_sparse(th0, phi_t, o_off, o_word, o_freq, lab_off, lab, iters=iters, alpha=alpha, top_m=0,
+                                              want=("theta",))["theta"]
+            theta_s = heldout.smooth_slots(th, w_obs, lab_off, alpha)
+            out = heldout.loglik_sparse(theta_s, phi_t, s_off, s_word, s_freq, lab_off, lab, weighted=weighted)
+        else:
+            th = self._fold_in_em_device(observed, start, iters, phi_t=phi_t)["theta"]
+            theta = heldout.smooth_theta(th, w_obs, alpha) if labels is None else \
+                heldout.smooth_theta_labels(th, w_obs, torch.from_numpy(start != 0.0).to(dev), alpha)
+            out = heldout.loglik(theta, phi_t, s_off, s_word, s_freq, weighted=weighted)
+        r = heldout.perplexity_from(*out)
+        return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped)
+
     # ---- left-to-right held-out likelihood (new; leftright.py, DESIGN.md 4.4f) ----
-    def left_to_right(self, newdocs, particles=10, labels=None, seed=None, stream_id=None, max_tokens=None):
+    def left_to_right(self, newdocs, particles=10, labels=None, seed=None, stream_id=None, max_tokens=None, sparse=False):
         """An estimate of p(w_d | ph_hat, alpha) for every held-out token list by the left-to-right particle sampler of Wallach et al.
         (2009): dict(perplexity, loglik, tokens, documents, skipped, bad).  The token lists keep the text's own order; tokens the
         dictionary does not know are dropped; ``max_tokens`` scores only the first tokens of every document.  Documents with no
@@ -602,25 +656,39 @@ class LabeledLDA(object):
         ``labels`` (one list of label strings per document): the topics of every document are restricted to its labels and
         'root' -- the figure is then p(w_d | labels_d).  perplexity = exp(-loglik / tokens), inf when a token had no finite positive
         probability (``bad`` counts them).  ``ph_hat`` stays on the device (llda_left_to_right); 32 bytes per document come back.
+        sparse=True (with ``labels``; at most 32 per document, root included -- ValueError beyond): through
+        llda_left_to_right_sparse, where a draw reads the document's own columns of phi only.  It works for every K the model can
+        have (the default raises above K = 1024) and gives the default's figure exactly where every label set is a prefix
+        0 .. L - 1; elsewhere the sums pair by slot and the estimate differs.
         Every rank scores the documents whole: no collective."""
         import torch
         from . import heldout, leftright
         if labels is not None and len(labels) != len(newdocs):
             raise ValueError("labels must hold one list per document of newdocs")
+        if sparse and labels is None:
+            raise ValueError("sparse=True wants the label sets: labels must be given")
         t2i = self.dicti.token2id
         lists, keep = leftright.prepare_tokens([[t2i[x] for x in doc if x in t2i] for doc in newdocs], max_tokens)
         skipped = len(newdocs) - len(keep)
         if not keep:
             return dict(perplexity=float("nan"), loglik=0.0, tokens=0, documents=0, skipped=skipped, bad=0)
-        allowed = None if labels is None else leftright.allowed_matrix([labels[d] for d in keep], self.labelmap, self.K)
+        sets = None
+        if sparse:
+            from . import attribution, docmodel
+            sets = docmodel.label_csr(attribution.explain_label_cols(self.labelmap, len(keep), labels=[labels[d] for d in keep]), K=self.K)
+            docmodel.label_sets(sets[0], sets[1], len(keep), self.K)        # (more than 32 labels in a document: ValueError, before any launch)
+        allowed = None if labels is None or sparse else leftright.allowed_matrix([labels[d] for d in keep], self.labelmap, self.K)
         ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
         dev = self._attr_device()
         ph_dev = ph.to(device=dev, dtype=torch.float64) if isinstance(ph, torch.Tensor) else \
             torch.from_numpy(np.ascontiguousarray(ph, dtype=np.float64)).to(dev)
         doc_off, word = leftright.tokens_csr(lists)
-        r = heldout.perplexity_from(*leftright.loglik(ph_dev.t().contiguous(), doc_off, word, float(self.alpha), particles,
-                                                      self.seed if seed is None else seed,
-                                                      leftright.LR_STREAM if stream_id is None else stream_id, allowed=allowed))
+        seed, stream_id = self.seed if seed is None else seed, leftright.LR_STREAM if stream_id is None else stream_id
+        if sparse:
+            out = leftright.loglik_sparse(ph_dev.t().contiguous(), doc_off, word, sets[0], sets[1], float(self.alpha), particles, seed, stream_id)
+        else:
+            out = leftright.loglik(ph_dev.t().contiguous(), doc_off, word, float(self.alpha), particles, seed, stream_id, allowed=allowed)
+        r = heldout.perplexity_from(*out)
         return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped,
                     bad=r["bad"])
 

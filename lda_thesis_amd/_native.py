@@ -172,6 +172,21 @@ class LldaWcreditSparseArgs(ctypes.Structure):
                 ("scratch", _c_p), ("scratch_bytes", _c_i64)]
 
 
+class LldaHeldoutSparseArgs(ctypes.Structure):
+    """struct llda_heldout_sparse_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("max_labels", _c_i32), ("reserved", _c_i32), ("doc_off", _c_p), ("word", _c_p),
+                ("freq", _c_p), ("lab_off", _c_p), ("lab", _c_p), ("theta_s", _c_p), ("phi_t", _c_p), ("D", _c_i64), ("V", _c_i64),
+                ("NL", _c_i64), ("ld_phi", _c_i64), ("mant", _c_p), ("expo", _c_p), ("tok", _c_p), ("bad", _c_p)]
+
+
+class LldaLeftrightSparseArgs(ctypes.Structure):
+    """struct llda_leftright_sparse_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("R", _c_i32), ("max_doc_tokens", _c_i32), ("doc_off", _c_p), ("word", _c_p),
+                ("phi_t", _c_p), ("lab_off", _c_p), ("lab", _c_p), ("doc_ids", _c_p), ("D", _c_i64), ("V", _c_i64), ("ld_phi", _c_i64),
+                ("NL", _c_i64), ("doc_base", _c_i64), ("alpha", _c_d), ("seed", _c_u64), ("stream_id", _c_u32), ("max_labels", _c_i32),
+                ("mant", _c_p), ("expo", _c_p), ("tok", _c_p), ("bad", _c_p), ("status", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -187,7 +202,9 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_wcredit_struct_bytes", "llda_credit_words_scratch_bytes", "llda_credit_words",
            "llda_phistep_struct_bytes", "llda_phi_step_scratch_bytes", "llda_phi_step",
            "llda_attr_sparse_struct_bytes", "llda_attribute_sparse",
-           "llda_wcredit_sparse_struct_bytes", "llda_credit_words_sparse_scratch_bytes", "llda_credit_words_sparse")
+           "llda_wcredit_sparse_struct_bytes", "llda_credit_words_sparse_scratch_bytes", "llda_credit_words_sparse",
+           "llda_heldout_sparse_struct_bytes", "llda_heldout_loglik_sparse",
+           "llda_leftright_sparse_struct_bytes", "llda_left_to_right_sparse")
 
 _LIB = None
 
@@ -331,6 +348,14 @@ def lib():
     L.llda_credit_words_sparse_scratch_bytes.argtypes = [_c_i64, _c_i64, _c_i32, _c_i32]
     L.llda_credit_words_sparse.restype = ctypes.c_int
     L.llda_credit_words_sparse.argtypes = [ctypes.POINTER(LldaWcreditSparseArgs), _c_p]
+    L.llda_heldout_sparse_struct_bytes.restype = ctypes.c_int
+    L.llda_heldout_sparse_struct_bytes.argtypes = []
+    L.llda_heldout_loglik_sparse.restype = ctypes.c_int
+    L.llda_heldout_loglik_sparse.argtypes = [ctypes.POINTER(LldaHeldoutSparseArgs), _c_p]
+    L.llda_leftright_sparse_struct_bytes.restype = ctypes.c_int
+    L.llda_leftright_sparse_struct_bytes.argtypes = []
+    L.llda_left_to_right_sparse.restype = ctypes.c_int
+    L.llda_left_to_right_sparse.argtypes = [ctypes.POINTER(LldaLeftrightSparseArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -354,7 +379,9 @@ def lib():
                                ("LldaWcreditArgs", LldaWcreditArgs, L.llda_wcredit_struct_bytes()),
                                ("LldaPhistepArgs", LldaPhistepArgs, L.llda_phistep_struct_bytes()),
                                ("LldaAttrSparseArgs", LldaAttrSparseArgs, L.llda_attr_sparse_struct_bytes()),
-                               ("LldaWcreditSparseArgs", LldaWcreditSparseArgs, L.llda_wcredit_sparse_struct_bytes())):
+                               ("LldaWcreditSparseArgs", LldaWcreditSparseArgs, L.llda_wcredit_sparse_struct_bytes()),
+                               ("LldaHeldoutSparseArgs", LldaHeldoutSparseArgs, L.llda_heldout_sparse_struct_bytes()),
+                               ("LldaLeftrightSparseArgs", LldaLeftrightSparseArgs, L.llda_leftright_sparse_struct_bytes())):
         if size != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
@@ -767,6 +794,28 @@ def left_to_right(doc_off, word, phi_t, D, V, K, *, particles, alpha, seed, stre
                           float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, 0, _ptr(mant), _ptr(expo),
                           _ptr(tok), _ptr(bad), _ptr(status))
     _launch(phi_t, lib().llda_left_to_right, "llda_left_to_right", ctypes.byref(a))
+
+
+def heldout_loglik_sparse(doc_off, word, freq, lab_off, lab, theta_s, phi_t, D, V, K, NL, max_labels, *, ld_phi=None, mant=None,
+                          expo=None, tok=None, bad=None):
+    """llda_heldout_loglik_sparse on the current torch stream: the sites as ``heldout_loglik`` takes them, the label sets and the loads
+    per slot as ``attribute_sparse`` does; mant (float64 [D]), expo, tok, bad (int64 [D]) the outputs, each may be None."""
+    a = LldaHeldoutSparseArgs(ctypes.sizeof(LldaHeldoutSparseArgs), int(K), int(max_labels), 0, _ptr(doc_off), _ptr(word), _ptr(freq),
+                              _ptr(lab_off), _ptr(lab), _ptr(theta_s), _ptr(phi_t), int(D), int(V), int(NL),
+                              int(phi_t.stride(0) if ld_phi is None else ld_phi), _ptr(mant), _ptr(expo), _ptr(tok), _ptr(bad))
+    _launch(phi_t, lib().llda_heldout_loglik_sparse, "llda_heldout_loglik_sparse", ctypes.byref(a))
+
+
+def left_to_right_sparse(doc_off, word, phi_t, lab_off, lab, D, V, K, NL, max_labels, *, particles, alpha, seed, stream_id, max_doc_tokens,
+                         mant, expo, tok, bad, ld_phi=None, doc_ids=None, doc_base=0, status=None):
+    """llda_left_to_right_sparse on the current torch stream: the tokens and the outputs as ``left_to_right`` takes them, the label
+    sets lab_off (int64 [D+1]) / lab (int32 [NL]) in place of the allowed rows; K up to LLDA_MAX_K."""
+    a = LldaLeftrightSparseArgs(ctypes.sizeof(LldaLeftrightSparseArgs), int(K), int(particles), int(max_doc_tokens), _ptr(doc_off),
+                                _ptr(word), _ptr(phi_t), _ptr(lab_off), _ptr(lab), _ptr(doc_ids), int(D), int(V),
+                                int(phi_t.stride(0) if ld_phi is None else ld_phi), int(NL), int(doc_base), float(alpha),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, int(max_labels), _ptr(mant), _ptr(expo),
+                                _ptr(tok), _ptr(bad), _ptr(status))
+    _launch(phi_t, lib().llda_left_to_right_sparse, "llda_left_to_right_sparse", ctypes.byref(a))
 
 
 NEAREST_MAX_N = 16            # LLDA_NEAREST_MAX_N

@@ -1,4 +1,4 @@
-// kernel_docsparse.hpp -- llda_attr_sparse_kernel, llda_wcredit_sparse_kernel: the document model on sparse label sets
+// kernel_docsparse.hpp -- llda_attr_sparse_kernel, llda_heldout_sparse_kernel, llda_wcredit_sparse_kernel: the document model on sparse label sets
 // Part of the single translation unit llda_gibbs.hip (included in order; see the contents list there).
 #pragma once
 
@@ -49,8 +49,8 @@ struct LabelSlot {
     double th;                                          // theta_s of the slot, 0.0 where there is none
 };
 
-// every lane of the group calls it (there is a ballot inside); have: d is a document
-template <int G>
+// every lane of the group calls it (there is a ballot inside); have: d is a document; LOADS: theta_s is given (else th = 0.0)
+template <int G, bool LOADS = true>
 __device__ __forceinline__ LabelSlot label_slot(const LabelSets &T, int64_t d, bool have, int gl, int K)
 {
     LabelSlot s;
@@ -66,7 +66,8 @@ __device__ __forceinline__ LabelSlot label_slot(const LabelSets &T, int64_t d, b
     s.fit = range && !(__ballot(wrong) & group);
     s.mine = s.fit && slot;
     s.k = s.mine ? k : 0;
-    s.th = s.mine ? T.theta_s[s.lb + gl] : 0.0;
+    if constexpr (LOADS) s.th = s.mine ? T.theta_s[s.lb + gl] : 0.0;
+    else s.th = 0.0;
     return s;
 }
 
@@ -121,6 +122,42 @@ __global__ void __launch_bounds__(64 * ATTR_WAVES) llda_attr_sparse_kernel(const
                 if (P.credit) P.credit[j] = 0.0;
             }
         if (g.active && g.gl == 0) attr_store(P, g.d, tok, bad);
+    }
+}
+
+// llda_heldout_loglik_sparse: llda_heldout_group_kernel with a label per lane and a label list per group.  p is
+// doc_tree<G> over the slots' products, the lanes >= L_d holding +0.0: sum64 of the compacted problem; heldout_site is unchanged.
+// An unfit document's sites arrive as NaN (all bad); L_d = 0 gives p = +0.0 at every site (all bad as well).
+struct HeldoutSparseParams : HeldoutParams {            // theta / ld_theta are not used: the slots take their place
+    LabelSets sets;
+};
+
+template <int G>
+__global__ void __launch_bounds__(64 * HELDOUT_WAVES) llda_heldout_sparse_kernel(const HeldoutSparseParams P, const int64_t n_tiles)
+{
+    constexpr int DPB = 64 * HELDOUT_WAVES / G;         // documents of a workgroup
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    GroupDoc g;
+    g.gl = threadIdx.x % G;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        g.d = tile * DPB + threadIdx.x / G;
+        g.active = g.d < P.D;
+        g.b = g.active ? P.doc_off[g.d] : 0;
+        g.n = g.active ? P.doc_off[g.d + 1] - g.b : 0;
+        g.n_max = g.n;                                  // the longest document of the wavefront
+#pragma unroll
+        for (int s = G; s < 64; s <<= 1) {
+            const int64_t o = __shfl_xor(g.n_max, s, 64);
+            g.n_max = o > g.n_max ? o : g.n_max;
+        }
+        const LabelSlot ls = label_slot<G>(P.sets, g.d, g.active, g.gl, P.K);
+        g.mine = ls.mine;
+        g.th = ls.th;
+        HeldoutDoc doc = {0.5, 1, 0, 0};
+        group_sites_at<G>(P, g, ls.k, ls.th, [&](int64_t, int32_t f, bool ok, bool live, double p, double) {
+            if (live) heldout_site(doc, (ls.fit && ok) ? p : nan, f);
+        });
+        if (g.active && g.gl == 0) heldout_store(P, g.d, doc);
     }
 }
 

@@ -59,6 +59,8 @@
 //   kernel_emfit.hpp    llda_wcredit_index / _wave / _lds / _group / _combine kernels   the E-step's shares added up per word, in chunks of a word's sites
 //                       llda_phistep_block / _den / _div kernels   the phi M-step: column sums in a fixed order, one division per entry
 //   kernel_docsparse.hpp llda_attr_sparse_kernel, llda_wcredit_sparse_kernel   both on sparse label sets: a lane per label of the document, the word's sums in LDS
+//                       llda_heldout_sparse_kernel   the likelihood of held-out sites against the loads per slot
+//   kernel_lrsparse.hpp llda_leftright_sparse_kernel   left-to-right on a document's own labels: one particle per lane group, one count per lane
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -102,6 +104,7 @@
 #include "kernel_ecdf.hpp"
 #include "kernel_emfit.hpp"
 #include "kernel_docsparse.hpp"
+#include "kernel_lrsparse.hpp"
 
 namespace {
 
@@ -1578,6 +1581,73 @@ int llda_credit_words_sparse(const llda_wcredit_sparse_args *a, void *stream)
     }
     hipLaunchKernelGGL(llda_wcredit_combine_kernel, doc_grid((a->V + WCREDIT_WAVES - 1) / WCREDIT_WAVES), dim3(64 * WCREDIT_WAVES), 0, st, P);
     return launched();
+}
+
+int llda_heldout_sparse_struct_bytes(void) { return (int)sizeof(llda_heldout_sparse_args); }
+int llda_leftright_sparse_struct_bytes(void) { return (int)sizeof(llda_leftright_sparse_args); }
+
+int llda_heldout_loglik_sparse(const llda_heldout_sparse_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_heldout_sparse_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->NL < 0 || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if (a->max_labels < 1 || a->max_labels > LLDA_SPARSE_MAX_LABELS) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->lab_off || !a->phi_t || (a->NL > 0 && (!a->lab || !a->theta_s))) return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->lab_off, a->theta_s, a->phi_t, a->tok, a->bad) || misaligned(7, a->mant, a->expo) ||
+        misaligned(3, a->word, a->freq, a->lab))
+        return LLDA_E_BAD_ARG;
+    HeldoutSparseParams P;
+    memset(&P, 0, sizeof P);
+    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.phi_t = a->phi_t;
+    P.D = a->D; P.V = a->V; P.ld_phi = a->ld_phi; P.K = a->K;
+    P.sets.lab_off = a->lab_off; P.sets.lab = a->lab; P.sets.theta_s = a->theta_s; P.sets.NL = a->NL; P.sets.max_labels = a->max_labels;
+    P.mant = a->mant; P.expo = a->expo; P.tok = a->tok; P.bad = a->bad;
+    hipStream_t st = (hipStream_t)stream;
+    return visit_int<8, 16, 32>(sparse_group(a->max_labels), [&](auto G) {
+        constexpr int docs = 64 * HELDOUT_WAVES / G.value;
+        const int64_t n_tiles = (P.D + docs - 1) / docs;
+        hipLaunchKernelGGL(llda_heldout_sparse_kernel<G.value>, doc_grid(n_tiles), dim3(64 * HELDOUT_WAVES), 0, st, P, n_tiles);
+        return launched();
+    });
+}
+
+int llda_left_to_right_sparse(const llda_leftright_sparse_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_leftright_sparse_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->NL < 0 || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if (a->max_labels < 1 || a->max_labels > LLDA_SPARSE_MAX_LABELS) return LLDA_E_BAD_ARG;
+    if (a->R < 1 || a->R > LLDA_LR_MAX_PARTICLES || !(a->alpha > 0.0) || !(a->alpha < INFINITY)) return LLDA_E_BAD_ARG;
+    if (a->max_doc_tokens < 1 || a->max_doc_tokens > LLDA_LR_MAX_TOKENS) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->lab_off || !a->phi_t || !a->mant || !a->expo || !a->tok || !a->bad || (a->NL > 0 && !a->lab))
+        return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->lab_off, a->phi_t, a->doc_ids, a->mant, a->expo, a->tok) || misaligned(7, a->bad) ||
+        misaligned(3, a->word, a->lab, a->status))
+        return LLDA_E_BAD_ARG;
+    static_assert(LLDA_SPARSE_MAX_LABELS <= LRS_NONE && LLDA_LR_MAX_PARTICLES * 32 == LRS_MAX_THREADS, "kernel_lrsparse.hpp restates the header");
+    LrSparseParams P;
+    memset(&P, 0, sizeof P);
+    P.doc_off = a->doc_off; P.word = a->word; P.phi_t = a->phi_t; P.doc_ids = a->doc_ids;
+    P.D = a->D; P.V = a->V; P.ld_phi = a->ld_phi; P.doc_base = a->doc_base;
+    P.K = a->K; P.R = a->R; P.cap = a->max_doc_tokens; P.alpha = a->alpha;
+    P.key0 = (uint32_t)a->seed; P.key1 = (uint32_t)(a->seed >> 32); P.stream_id = a->stream_id;
+    P.mant = a->mant; P.expo = a->expo; P.tok = a->tok; P.bad = a->bad; P.status = a->status;
+    P.sets.lab_off = a->lab_off; P.sets.lab = a->lab; P.sets.NL = a->NL; P.sets.max_labels = a->max_labels;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = lrs_lds_bytes(P.R, P.cap);                           // at most 82 176 bytes
+    const dim3 grid((unsigned)(P.D < (1 << 20) ? P.D : (1 << 20)));
+    return visit_int<8, 16, 32>(sparse_group(a->max_labels), [&](auto G) {
+        const auto kern = llda_leftright_sparse_kernel<G.value>;
+        const int rl = allow_lds(kern, lds);
+        if (rl) return rl;
+        const int waves = (P.R * G.value + 63) / 64;                        // 64 / G particles per wavefront
+        hipLaunchKernelGGL(kern, grid, dim3(64 * waves), lds, st, P);
+        return launched();
+    });
 }
 
 int64_t llda_phi_step_scratch_bytes(int64_t V, int32_t K)

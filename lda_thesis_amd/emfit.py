@@ -194,12 +194,15 @@ def fit(theta0, phi_t0, doc_off, word, freq, alpha, beta, iters, theta_steps=1, 
     return dict(theta=theta, phi_t=phi_t, iterations=iters, trace=trace)
 
 
-def fit_sparse(theta_s0, phi_t0, doc_off, word, freq, lab_off, lab, alpha, beta, iters, theta_steps=1, chunk=DEFAULT_CHUNK, trace_every=0):
+def fit_sparse(theta_s0, phi_t0, doc_off, word, freq, lab_off, lab, alpha, beta, iters, theta_steps=1, chunk=DEFAULT_CHUNK, trace_every=0,
+               sparse_trace=False):
     """``fit`` for documents that carry a few of the K labels: the same loop on ``llda_attribute_sparse`` and
     ``llda_credit_words_sparse`` plus the unchanged ``phi_step``.  theta_s0 (float64 [NL], on the device) holds the start loads per
     slot of the label CSR lab_off / lab (``docmodel.label_csr``); phi_t0 is (V, K).  A site costs len(labels) gathered entries on
-    either side, whatever K is.  The trace is ``heldout.loglik`` on the loads scattered to (D, K).  Returns dict(theta_s [NL],
-    phi_t (V, K), theta (D, K): theta_s scattered, +0.0 outside the label sets; iterations, trace)."""
+    either side, whatever K is.  The trace is ``heldout.loglik`` on the loads scattered to (D, K); sparse_trace=True:
+    ``heldout.loglik_sparse`` on the slots themselves (no (D, K) matrix; its sums pair by slot, so the figures differ from the
+    default's in their last bits).  Returns dict(theta_s [NL], phi_t (V, K), theta (D, K): theta_s scattered, +0.0 outside the
+    label sets; iterations, trace)."""
     import torch
     from . import attribution, heldout
     _native.lib()
@@ -236,6 +239,9 @@ def fit_sparse(theta_s0, phi_t0, doc_off, word, freq, lab_off, lab, alpha, beta,
                                     scratch if S else None, ld_phi=K, ld_credit=K, credit_w=cw)
         _native.phi_step(cw, V, K, beta, phi_t, scratch, ld=K, ld_out=K)
         if trace_every and it % trace_every == 0:
-            r = heldout.perplexity_from(*heldout.loglik(attribution.scatter_slots(theta_s, off_h, lab_h, K), phi_t, d_off, d_word, d_freq))
+            if sparse_trace:
+                r = heldout.perplexity_from(*heldout.loglik_sparse(theta_s, phi_t, d_off, d_word, d_freq, off_h, lab_h))
+            else:
+                r = heldout.perplexity_from(*heldout.loglik(attribution.scatter_slots(theta_s, off_h, lab_h, K), phi_t, d_off, d_word, d_freq))
             trace.append((it, r["loglik"], r["tokens"], r["bad"]))
     return dict(theta_s=theta_s[:NL], phi_t=phi_t, theta=attribution.scatter_slots(theta_s, off_h, lab_h, K), iterations=iters, trace=trace)

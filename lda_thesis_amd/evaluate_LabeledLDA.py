@@ -52,6 +52,13 @@ def build_parser():
     p.add_option("--left-to-right", dest="left_to_right", type="int", default=0, metavar="R",
                  help="after the report: perplexity of the held-out documents from the left-to-right estimate of their likelihood "
                       "with R particles (Wallach et al. 2009; llda_left_to_right)")
+    p.add_option("--lr-sparse", action="store_true", dest="lr_sparse", default=False,
+                 help="with --left-to-right: score every test document against its own labels (the ones the model knows, and "
+                      "'root') through the sparse-label kernel (llda_left_to_right_sparse): p(w_d | labels_d), for every K")
+    p.add_option("--heldout-em", dest="heldout_em", type="int", default=0, metavar="ITERS",
+                 help="after the report: perplexity of the held-out documents by document completion without random numbers: the "
+                      "observed half folded in by ITERS EM steps (llda_attribute, llda_heldout_loglik); with --em-sparse against "
+                      "the documents' own labels through the sparse-label kernels (llda_attribute_sparse, llda_heldout_loglik_sparse)")
     p.add_option("--em-foldin", dest="em_foldin", type="int", default=0, metavar="ITERS",
                  help="after the report: the same four metrics for the loads of the deterministic EM fold-in with ITERS steps "
                       "(llda_attribute), ranked and scored on the GPU")
@@ -166,11 +173,18 @@ def report_explain(model, test, n_docs, iters):
             print("  %-24s %8.2f  %s" % (label, credit[label], " ".join(best)))
 
 
-def report_left_to_right(model, test, particles):
-    """held-out perplexity of the test documents from the left-to-right estimate of p(w_d | phi, alpha)"""
-    r = model.left_to_right(test[0], particles=particles)
+def known_labels(model, test):
+    """the labels of every test document that the model has a topic for"""
+    return [[x for x in labs if x in model.labelmap] for labs in test[1]]
+
+
+def report_left_to_right(model, test, particles, sparse=False):
+    """held-out perplexity of the test documents from the left-to-right estimate of p(w_d | phi, alpha); sparse: of p(w_d | labels_d),
+    every document against its own labels"""
+    r = model.left_to_right(test[0], particles=particles, labels=known_labels(model, test), sparse=True) if sparse else \
+        model.left_to_right(test[0], particles=particles)
     print("-----------------------------------")
-    print("Held-out perplexity (left-to-right, %d particles): " % particles, r["perplexity"])
+    print("Held-out perplexity (left-to-right%s, %d particles): " % (", own labels" if sparse else "", particles), r["perplexity"])
     print("  scored tokens %d in %d documents (%d skipped, %d bad tokens), log-likelihood %s"
           % (r["tokens"], r["documents"], r["skipped"], r["bad"], r["loglik"]))
     return r
@@ -182,6 +196,19 @@ def report_heldout(model, test, it, thinning):
     r = model.heldout_perplexity([[x for x in doc if x in known] for doc in test[0]], it, thinning)
     print("-----------------------------------")
     print("Held-out perplexity (document completion): ", r["perplexity"])
+    print("  scored tokens %d in %d documents (%d skipped), log-likelihood %s" % (r["tokens"], r["documents"], r["skipped"], r["loglik"]))
+    return r
+
+
+def report_heldout_em(model, test, iters, sparse=False):
+    """held-out perplexity by document completion with the EM fold-in (LabeledLDA.heldout_perplexity_em); sparse: against the
+    documents' own labels, through the sparse-label kernels"""
+    known = set(model.vocab)
+    docs = [[x for x in doc if x in known] for doc in test[0]]
+    r = model.heldout_perplexity_em(docs, iters=iters, labels=known_labels(model, test), sparse=True) if sparse else \
+        model.heldout_perplexity_em(docs, iters=iters)
+    print("-----------------------------------")
+    print("Held-out perplexity (document completion, EM fold-in of %d steps%s): " % (iters, ", own labels" if sparse else ""), r["perplexity"])
     print("  scored tokens %d in %d documents (%d skipped), log-likelihood %s" % (r["tokens"], r["documents"], r["skipped"], r["loglik"]))
     return r
 
@@ -318,7 +345,9 @@ def main(argv=None):
     if opt.heldout_perplexity:
         report_heldout(model, test, opt.it, opt.thinning)
     if opt.left_to_right:
-        report_left_to_right(model, test, opt.left_to_right)
+        report_left_to_right(model, test, opt.left_to_right, sparse=opt.lr_sparse)
+    if opt.heldout_em:
+        report_heldout_em(model, test, opt.heldout_em, sparse=opt.em_sparse)
     if opt.em_foldin:
         report_em_foldin(model, test, opt.em_foldin)
     if opt.explain:

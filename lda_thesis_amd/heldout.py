@@ -59,6 +59,62 @@ def loglik(theta_dev, phi_t_dev, doc_off, word, freq, weighted=True):
     return mant.cpu().numpy(), expo.cpu().numpy(), tok.cpu().numpy(), bad.cpu().numpy()
 
 
+def loglik_sparse(theta_s, phi_t_dev, doc_off, word, freq, lab_off, lab, weighted=True):
+    """``loglik`` for documents that carry a few of the K labels (``llda_heldout_loglik_sparse``): the label sets are
+    the CSR lab_off (int64 [D+1]) / lab (``docmodel.label_csr``), theta_s (float64 [NL], on the device) the loads per slot.  A site
+    reads len(labels) entries of its word's row of phi_t_dev (V, K), not K, and no (D, K) matrix exists.  Returns the same
+    (mant, expo, tok, bad).  ValueError on the host, before any launch, for label sets the kernel would call unfit."""
+    import torch
+    from . import attribution
+    _native.lib()
+    _native.require_device()
+    phi_t_dev = docmodel.matrix(phi_t_dev, "phi_t")
+    V, K = int(phi_t_dev.shape[0]), int(phi_t_dev.shape[1])
+    dev = phi_t_dev.device
+    _, D, S = docmodel.check_offsets(doc_off)
+    off_h, lab_h, NL, max_labels = docmodel.label_sets(lab_off, lab, D, K)
+    theta_s = attribution._slots(theta_s, NL, dev, "theta_s")
+    d_off, d_word, d_freq = docmodel.stage(dev, doc_off, word, freq if weighted else None, S, V)
+    d_loff, d_lab = docmodel.on_dev(off_h, torch.int64, dev), docmodel.on_dev(lab_h if NL else np.zeros(1), torch.int32, dev)
+    mant = torch.empty((D,), dtype=torch.float64, device=dev)
+    expo, tok, bad = (torch.empty((D,), dtype=torch.int64, device=dev) for _ in range(3))
+    _native.heldout_loglik_sparse(d_off, d_word, d_freq, d_loff, d_lab, theta_s, phi_t_dev, D, V, K, NL, max_labels,
+                                  ld_phi=int(phi_t_dev.stride(0)) if V > 1 else K, mant=mant, expo=expo, tok=tok, bad=bad)
+    return mant.cpu().numpy(), expo.cpu().numpy(), tok.cpu().numpy(), bad.cpu().numpy()
+
+
+def smooth_slots(th_s, w_obs, lab_off, alpha):
+    """``smooth_theta`` per slot of a label CSR, with a document's label count L_d in place of K:  (W_d * th + alpha) / (W_d + L_d *
+    alpha) at every slot of document d.  th_s [NL], w_obs [D] and lab_off [D+1] (host offsets): numpy arrays, or th_s / w_obs torch
+    tensors on one device -- the same IEEE operations in the same order either way."""
+    off_h = np.asarray(lab_off, dtype=np.int64)
+    counts = np.diff(off_h)
+    den = w_obs + _like(counts.astype(np.float64), w_obs) * alpha
+    rows = _like(np.repeat(np.arange(off_h.shape[0] - 1, dtype=np.int64), counts), w_obs)
+    return (w_obs[rows] * th_s[:int(off_h[-1])] + alpha) / den[rows]
+
+
+def smooth_theta_labels(th, w_obs, allowed, alpha):
+    """``smooth_theta`` on label sets: (W_d * th + alpha) / (W_d + L_d * alpha) on the allowed columns (``allowed`` (D, K), non-zero =
+    allowed; L_d = how many) and +0.0 elsewhere.  numpy arrays or torch tensors on one device."""
+    on = allowed != 0
+    tensors = not isinstance(th, np.ndarray)
+    L = on.sum(1).to(th.dtype) if tensors else on.sum(1).astype(np.float64)
+    full = (w_obs[:, None] * th + alpha) / (w_obs + L * alpha)[:, None]
+    if tensors:
+        import torch
+        return torch.where(on, full, torch.zeros_like(full))
+    return np.where(on, full, 0.0)
+
+
+def _like(a, ref):
+    """the numpy array a as ref is: a numpy array, or a tensor on ref's device"""
+    if hasattr(ref, "device") and not isinstance(ref, np.ndarray):
+        import torch
+        return torch.from_numpy(a).to(ref.device)
+    return a
+
+
 _LN2 = math.log(2.0)
 
 

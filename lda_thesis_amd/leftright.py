@@ -100,3 +100,41 @@ def loglik(phi_t_dev, doc_off, word, alpha, particles, seed, stream_id=LR_STREAM
     if int(status.item()) & 1:
         raise _native.NativeError("llda_left_to_right: a document was longer than the launch allowed")
     return out
+
+
+def loglik_sparse(phi_t_dev, doc_off, word, lab_off, lab, alpha, particles, seed, stream_id=LR_STREAM, doc_ids=None):
+    """``loglik`` with every document's topics restricted to its own label list (``llda_left_to_right_sparse``): the
+    lists are the CSR lab_off (int64 [D+1]) / lab (``docmodel.label_csr``: ids ascending, at most 32 per document).  A draw touches
+    len(labels) entries of the word's row of phi_t_dev (V, K), whatever K is -- K may be anything up to the library's limit, not
+    1024.  The result is that of ``loglik`` on the document's own columns of phi_t.  Returns the per-document (mant, expo, tok,
+    bad); ValueError on the host, before any launch, for label sets the kernel would call unfit."""
+    import torch
+    _native.lib()
+    _native.require_device()
+    x = docmodel.matrix(phi_t_dev, "phi_t")
+    dev = x.device
+    V, K = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= int(particles) <= MAX_PARTICLES:
+        raise ValueError("particles must be in 1 .. %d" % MAX_PARTICLES)
+    off_h, D, S = docmodel.check_offsets(doc_off)
+    loff_h, lab_h, NL, max_labels = docmodel.label_sets(lab_off, lab, D, K)
+    longest = int(np.diff(off_h).max()) if D else 0
+    if longest > MAX_TOKENS:
+        raise ValueError("a document holds %d tokens, more than %d" % (longest, MAX_TOKENS))
+    d_off, d_word, _ = docmodel.stage(dev, off_h, word, None, S, unit="tokens")
+    d_loff, d_lab = docmodel.on_dev(loff_h, torch.int64, dev), docmodel.on_dev(lab_h if NL else np.zeros(1), torch.int32, dev)
+    d_ids = None
+    if doc_ids is not None:
+        d_ids = docmodel.on_dev(doc_ids, torch.int64, dev)
+        if int(d_ids.numel()) != D:
+            raise ValueError("doc_ids must hold D = %d ids" % D)
+    mant = torch.empty((D,), dtype=torch.float64, device=dev)
+    expo, tok, bad = (torch.empty((D,), dtype=torch.int64, device=dev) for _ in range(3))
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _native.left_to_right_sparse(d_off, d_word, x, d_loff, d_lab, D, V, K, NL, max_labels, particles=int(particles), alpha=float(alpha),
+                                 seed=seed, stream_id=stream_id, max_doc_tokens=max(1, longest), mant=mant, expo=expo, tok=tok, bad=bad,
+                                 ld_phi=int(x.stride(0)) if V > 1 else K, doc_ids=d_ids, status=status)
+    out = mant.cpu().numpy(), expo.cpu().numpy(), tok.cpu().numpy(), bad.cpu().numpy()
+    if int(status.item()) & 1:
+        raise _native.NativeError("llda_left_to_right_sparse: a document was longer than the launch allowed")
+    return out
