@@ -1280,6 +1280,56 @@ typedef struct llda_leftright_sparse_args {
 int llda_leftright_sparse_struct_bytes(void);
 int llda_left_to_right_sparse(const llda_leftright_sparse_args *args, void *stream);
 
+/* llda_foldin_sparse (additive to ABI 22): the test-time sampler of llda_foldin for documents that carry a handful of
+ * the K labels, for every K in 1 .. LLDA_MAX_K.  The label sets are lab_off, lab, NL, max_labels as above (no loads); phi_t is the
+ * word-major matrix in reference topic order that the document model reads, not llda_foldin's lane-major ph.  A site costs L_d
+ * gathered doubles per sweep, whatever K is.
+ * Arithmetic: the text of llda_foldin (beta_fallback = 0, avg_mode = 0, beta = 0) on the document's compacted problem -- K' = L_d,
+ * ph'[j][v] = phi_t[v][lab[j]], in the layout of K' topics: one numpy leaf, compacted topic j in lane j & 7, slot j >> 3.
+ *   sum      numpy's order for L_d contiguous doubles: sequential for L_d < 8, else L_d / 8 rows on eight chains, the xor butterfly
+ *            1, 2, 4, then the L_d % 8 tail in order.
+ *   draw     the keyed draw on that layout with u(seed; sweep, stream_id, doc, n), doc = doc_ids[d] or doc_base + d (low 32 bits).
+ *   start    sweep word 0xFFFFFFFF.  Every column ph'[:, v] is divided by its own sum over the L_d labels; a document that holds a
+ *            column which cannot be normalised (sum 0, or a quotient that is not finite) starts every site from the uniform row
+ *            1 / L_d.  Then `while sum > 1: prob /= c_init`, draw.
+ *   sweep i  prob = (n_dk + alpha) * ph'[:, v]; S = sum; prob /= S; `while sum > 1: prob /= c_loop`; draw.  Every site takes this
+ *            pipeline (no decided tier); the quotients are IEEE divisions over the whole range of doubles.
+ *   average  after every sweep i with (i + 1) % thinning == 0: cur = n_dk / n_dk.sum(), avg = cur for the first, else
+ *            (s-1)/s * avg + (1/s) * cur with s = (i + 1) / thinning, each product rounded on its own.  th_s = 0 when there is none.
+ * Outputs: z [S] the SLOT j of the document's list (not a topic id); n_dk_s, th_s [NL] per slot.
+ * An UNFIT document (offsets outside [0, NL], L_d > max_labels, an id outside [0, K), ids that do not ascend strictly): z = -1 at all
+ * its sites, nothing else of it is written, none of its ids is used as an index; status bit 2.  A site whose word is outside [0, V):
+ * z = -1, it adds nothing to the counts, is never used as an index and keeps its site number n; status bit 1.  A site with no
+ * positive probability (every site of a fit document with L_d = 0 among them): status bit 0, the document's other outputs are then
+ * unspecified.  A document without sites: n_dk_s = 0, th_s = 0.  D == 0: nothing to do.
+ * 8 lanes per document, 1, 2 or 4 slots per lane by max_labels; a document's outputs depend on its own sites, its id, its label list
+ * and the scalars only, not on D or its place in the batch; tests/sparsefoldinref.py restates them.
+ * LLDA_E_BAD_K: K outside 1 .. LLDA_MAX_K.  LLDA_E_BAD_ARG: NULL args or a struct_bytes that is not the struct's; D < 0; V outside
+ * 1 .. 2^31 - 1; NL < 0; ld_phi < K; max_labels outside 1 .. LLDA_SPARSE_MAX_LABELS; iters < 0; thinning < 1; c_init or c_loop not
+ * > 1; alpha NaN; with D > 0 a NULL doc_off, word, freq, lab_off, phi_t or z, or (NL > 0) a NULL lab, n_dk_s or th_s; a misaligned
+ * pointer.  All before anything touches HIP. */
+typedef struct llda_foldin_sparse_args {
+    uint32_t struct_bytes;       /* sizeof(llda_foldin_sparse_args)                              */
+    int32_t  K, max_labels, iters, thinning;
+    uint32_t stream_id;
+    const int64_t *doc_off;      /* [dev] [D+1]                                                  */
+    const int32_t *word;         /* [dev] [S]                                                    */
+    const int32_t *freq;         /* [dev] [S]                                                    */
+    const double  *phi_t;        /* [dev] [V][ld_phi]                                            */
+    const int64_t *lab_off;      /* [dev] [D+1]                                                  */
+    const int32_t *lab;          /* [dev] [NL]                                                   */
+    const int64_t *doc_ids;      /* [dev] [D] or NULL                                            */
+    int64_t  D, V, NL, ld_phi, doc_base;
+    double   alpha, c_init, c_loop;
+    uint64_t seed;
+    int32_t *z;                  /* [dev] [S]  out: the slot of every site, -1 = none            */
+    int32_t *n_dk_s;             /* [dev] [NL] out                                               */
+    double  *th_s;               /* [dev] [NL] out                                               */
+    int32_t *status;             /* [dev] [1] or NULL                                            */
+} llda_foldin_sparse_args;
+int llda_foldin_sparse_struct_bytes(void);
+int llda_foldin_sparse(const llda_foldin_sparse_args *args, void *stream);
+
 /* Device self test of the kernel's division shortcut: runs >= n random (a, b) pairs through
  * "q = a * RN(1/b) + two exact-residual corrections" and through the hardware IEEE division and adds
  * the number of differing results to *mismatches_dev (dev, uint64, zeroed by the caller).  Expected: 0. */

@@ -508,10 +508,17 @@ class LabeledLDA(object):
         ids, freqs = zip(*tups)
         return ids, freqs, list(r["z"][0]), r["n_dk"][0]
 
-    def run_test(self, newdocs, it, thinning, seed=None, stream_id=None):
+    def run_test(self, newdocs, it, thinning, seed=None, stream_id=None, candidates=None):
         """thinned average of n_dk / sum(n_dk) over ``it`` fold-in sweeps per held-out document
-        (LabeledLDA.py:179-212); all documents and sweeps in one llda_foldin launch."""
+        (LabeledLDA.py:179-212); all documents and sweeps in one llda_foldin launch.
+        ``candidates`` (new; one list of label strings per document): the sampler runs over 'root' plus those labels only
+        (llda_foldin_sparse; at most 32 per document, root included) and the (D, K) loads are +0.0 outside the lists.
+        With every label as a candidate the loads are those of the default, bit for bit."""
         from .foldin import TEST_STREAM, fold_in
+        if candidates is not None:
+            from . import attribution
+            th_s, lab_off, lab = self._test_slots_device(newdocs, it, thinning, seed, stream_id, candidates, None)
+            return attribution.scatter_slots(th_s, lab_off, lab, self.K).cpu().numpy()
         tups = [self.dicti.doc2bow(x) for x in newdocs]
         ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat     # still on the device after training
         r = fold_in(ph, self.alpha, tups, it, thinning, self.seed if seed is None else seed,
@@ -536,28 +543,95 @@ class LabeledLDA(object):
         return fold_in(ph, self.alpha, tups, it, thinning, self.seed if seed is None else seed,
                        TEST_STREAM if stream_id is None else stream_id, keep_device=True)
 
-    def predict(self, newdocs, it, thinning, n=5, seed=None, stream_id=None):
+    def _test_phi_t_device(self):
+        """ph_hat as ``run_test`` reads it, word-major (V, K) on the device"""
+        import torch
+        ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
+        if not isinstance(ph, torch.Tensor):
+            ph = torch.from_numpy(np.ascontiguousarray(ph, dtype=np.float64))
+        return ph.to(device=self._attr_device(), dtype=torch.float64).t().contiguous()
+
+    def shortlist_cols(self, tups, m, phi_t=None):
+        """The shortlist of every doc2bow list: column 0 ('root') plus the m <= 16 labels with the most credit after ONE attribution
+        pass from uniform loads (llda_attribute with no EM step, then llda_rank_labels without the root; equal credit by label
+        index).  Columns ascending.  Nothing of size (D, K) comes to the host."""
+        from . import attribution, ranking
+        if not 1 <= int(m) <= ranking.MAX_TOP_N:
+            raise ValueError("shortlist must be in 1 .. %d" % ranking.MAX_TOP_N)
+        self._check_tups(tups)
+        D = len(tups)
+        if D == 0:
+            return []
+        credit = self._fold_in_em_device(tups, attribution.uniform_start(None, D, self.K), 0, want=("credit",),
+                                         phi_t=self._test_phi_t_device() if phi_t is None else phi_t)["credit"]
+        ranked = ranking.rank_labels(credit, None, first=1, top_n=int(m)).host()["top_idx"]
+        return [[0] + sorted(int(k) for k in row if int(k) >= 1) for row in ranked]
+
+    def _test_slots_device(self, newdocs, it, thinning, seed, stream_id, candidates, shortlist):
+        """the fold-in on label lists: (th_s [NL] on the device, lab_off, lab on the host).  candidates: label strings per document;
+        shortlist: m, the lists are built on the device (``shortlist_cols``)."""
+        from . import attribution, docmodel
+        from .foldin import TEST_STREAM, fold_in_sparse
+        if candidates is not None and shortlist is not None:
+            raise ValueError("candidates and shortlist exclude one another")
+        tups = [self.dicti.doc2bow(x) for x in newdocs]
+        phi_t = self._test_phi_t_device()
+        if candidates is not None:
+            cols = attribution.explain_label_cols(self.labelmap, len(tups), labels=candidates)
+        else:
+            cols = self.shortlist_cols(tups, shortlist, phi_t=phi_t)
+        lab_off, lab = docmodel.label_csr(cols, K=self.K)
+        th_s, _, _ = fold_in_sparse(phi_t, self.alpha, tups, lab_off, lab, it, thinning, self.seed if seed is None else seed,
+                                    TEST_STREAM if stream_id is None else stream_id, keep_device=True)
+        return th_s, lab_off, lab
+
+    def predict(self, newdocs, it, thinning, n=5, seed=None, stream_id=None, candidates=None, shortlist=None):
         """``get_preds(run_test(newdocs, it, thinning), n)`` with the ranking on the device (llda_rank_labels): the fold-in's loads
         never leave it, only the n (label, load) pairs per document do.  n <= 16.  Equal loads are ordered by label index
-        ascending (``get_pred``'s argsort leaves their order open); the loads themselves are the same bits."""
+        ascending (``get_pred``'s argsort leaves their order open); the loads themselves are the same bits.
+        ``candidates`` (label strings per document) or ``shortlist`` = m in 1 .. 16 (new): the sampler runs on
+        'root' plus the candidates, or plus the m labels one attribution pass credits most (``shortlist_cols``), through
+        llda_foldin_sparse.  The slots are ranked on a padded (D, longest list) matrix, the same tie rule; no (D, K) matrix is formed,
+        and a document gets min(n, its list) pairs."""
         from . import ranking
+        if candidates is not None or shortlist is not None:
+            import torch
+            th_s, lab_off, lab = self._test_slots_device(newdocs, it, thinning, seed, stream_id, candidates, shortlist)
+            D, counts = len(lab_off) - 1, np.diff(lab_off)
+            width = int(counts.max()) if D else 0
+            dev = th_s.device
+            rows = torch.from_numpy(np.repeat(np.arange(D, dtype=np.int64), counts)).to(dev)
+            at = torch.from_numpy(np.arange(int(lab_off[-1]), dtype=np.int64) - np.repeat(lab_off[:-1], counts)).to(dev)
+            pad = torch.full((D, width), float("-inf"), dtype=torch.float64, device=dev)
+            pad[rows, at] = th_s
+            val, order = torch.sort(pad, dim=1, descending=True, stable=True)        # (slots ascend in label id: ties by label index)
+            m = min(int(n), width)
+            val, order = val[:, :m].cpu().numpy(), order[:, :m].cpu().numpy()
+            names = np.array(list(self.labelmap.keys()))
+            return [list(zip(names[lab[lab_off[d] + order[d, :min(m, counts[d])]]], val[d, :min(m, counts[d])])) for d in range(D)]
         th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
         r = ranking.rank_labels(th, None, first=0, top_n=n).host()
         names = np.array(list(self.labelmap.keys()))
         m = min(n, self.K)
         return [list(zip(names[idx[:m]], val[:m])) for idx, val in zip(r["top_idx"], r["top_val"])]
 
-    def score_test(self, newdocs, labels, it, thinning, seed=None, stream_id=None):
+    def score_test(self, newdocs, labels, it, thinning, seed=None, stream_id=None, candidates=None, shortlist=None):
         """Fold ``newdocs`` in and score the loads against ``labels`` (one list of label strings per document, what
         ``evaluate.binary_yreal`` takes) by the rules of the harness's report: dict(auc, one_error, two_error, f1, kept, dropped)
-        (``ranking.metrics``).  Per document 28 bytes come back to the host."""
+        (``ranking.metrics``).  Per document 28 bytes come back to the host.  ``candidates`` / ``shortlist``: as in ``predict``; the
+        loads are +0.0 outside the lists."""
         from . import ranking
         from .evaluate import binary_yreal
-        th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
+        if candidates is not None or shortlist is not None:
+            from . import attribution
+            th_s, lab_off, lab = self._test_slots_device(newdocs, it, thinning, seed, stream_id, candidates, shortlist)
+            th = attribution.scatter_slots(th_s, lab_off, lab, self.K)
+        else:
+            th = self._test_theta_device(newdocs, it, thinning, seed, stream_id)
         return ranking.metrics(ranking.rank_labels(th, binary_yreal(labels, self.labelmap), first=1, top_n=0))
 
     # ---- held-out perplexity by document completion (new; heldout.py, DESIGN.md 4.4d) ----
-    def heldout_perplexity(self, newdocs, it, thinning, weighted=True, seed=None, stream_id=None, scored_docs=None):
+    def heldout_perplexity(self, newdocs, it, thinning, weighted=True, seed=None, stream_id=None, scored_docs=None, labels=None):
         """How well the trained model predicts unseen text: dict(perplexity, loglik, tokens, documents, skipped).
         Every held-out token list goes through ``dicti.doc2bow``; its sites 0, 2, 4, ... are folded in exactly as ``run_test`` folds
         documents in (same seed and stream conventions, document ids 0, 1, ... over the documents that are kept), the loads are
@@ -568,10 +642,16 @@ class LabeledLDA(object):
         dropped and counted as ``skipped``; a document with nothing to score contributes no tokens.  perplexity is inf when a scored
         site has no finite positive probability, nan when no token was scored.
         ``ph_hat`` and the loads stay on the device (llda_foldin, llda_heldout_loglik); 32 bytes per document come back.  The
-        documents are scored whole on every rank: no collective."""
+        documents are scored whole on every rank: no collective.
+        ``labels`` (new; one list of label strings per document): the label-conditioned figure by sampling.  The observed halves
+        are folded in over 'root' plus the document's own labels (llda_foldin_sparse; at most 32 per document), the loads are
+        smoothed per slot with L_d in K's place (``heldout.smooth_slots``) and scored by ``heldout.loglik_sparse``; split, skip rules,
+        ids and streams are the default's."""
         import torch
         from . import heldout
         from .foldin import TEST_STREAM, fold_in
+        if labels is not None and len(labels) != len(newdocs):
+            raise ValueError("labels must hold one list per document of newdocs")
         tups = [self.dicti.doc2bow(x) for x in newdocs]
         if scored_docs is None:
             observed, scored = heldout.completion_split(tups)
@@ -584,6 +664,19 @@ class LabeledLDA(object):
         if not keep:
             return dict(perplexity=float("nan"), loglik=0.0, tokens=0, documents=0, skipped=skipped)
         observed, scored = [observed[d] for d in keep], [scored[d] for d in keep]
+        if labels is not None:
+            from . import attribution, docmodel
+            from .foldin import fold_in_sparse
+            cols = attribution.explain_label_cols(self.labelmap, len(keep), labels=[labels[d] for d in keep])
+            lab_off, lab = docmodel.label_csr(cols, K=self.K)
+            phi_t = self._test_phi_t_device()
+            th_s, _, _ = fold_in_sparse(phi_t, self.alpha, observed, lab_off, lab, it, thinning, self.seed if seed is None else seed,
+                                        TEST_STREAM if stream_id is None else stream_id, keep_device=True)
+            w_obs = torch.from_numpy(heldout.observed_tokens(observed)).to(th_s.device)
+            theta_s = heldout.smooth_slots(th_s, w_obs, lab_off, float(self.alpha))
+            s_off, s_word, s_freq = csr_from_doc_tups(scored)
+            r = heldout.perplexity_from(*heldout.loglik_sparse(theta_s, phi_t, s_off, s_word, s_freq, lab_off, lab, weighted=weighted))
+            return dict(perplexity=r["perplexity"], loglik=r["loglik"], tokens=r["tokens"], documents=len(keep), skipped=skipped)
         ph = self._ph_hat.dev if self._ph_hat.dev is not None else self.ph_hat
         th = fold_in(ph, self.alpha, observed, it, thinning, self.seed if seed is None else seed,
                      TEST_STREAM if stream_id is None else stream_id, keep_device=True)

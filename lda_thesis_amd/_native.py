@@ -187,6 +187,14 @@ class LldaLeftrightSparseArgs(ctypes.Structure):
                 ("mant", _c_p), ("expo", _c_p), ("tok", _c_p), ("bad", _c_p), ("status", _c_p)]
 
 
+class LldaFoldinSparseArgs(ctypes.Structure):
+    """struct llda_foldin_sparse_args (include/llda_gibbs.h)."""
+    _fields_ = [("struct_bytes", _c_u32), ("K", _c_i32), ("max_labels", _c_i32), ("iters", _c_i32), ("thinning", _c_i32),
+                ("stream_id", _c_u32), ("doc_off", _c_p), ("word", _c_p), ("freq", _c_p), ("phi_t", _c_p), ("lab_off", _c_p), ("lab", _c_p),
+                ("doc_ids", _c_p), ("D", _c_i64), ("V", _c_i64), ("NL", _c_i64), ("ld_phi", _c_i64), ("doc_base", _c_i64), ("alpha", _c_d),
+                ("c_init", _c_d), ("c_loop", _c_d), ("seed", _c_u64), ("z", _c_p), ("n_dk_s", _c_p), ("th_s", _c_p), ("status", _c_p)]
+
+
 EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hip_error", "llda_struct_size", "llda_layout_init",
            "llda_sweep_scratch_bytes", "llda_rows16_ok", "llda_quad_ok", "llda_pack_rows16", "llda_pack_rows16_all", "llda_pack_image", "llda_pack_image_cols",
 
@@ -204,7 +212,8 @@ EXPORTS = ("llda_abi_version", "llda_build_info", "llda_strerror", "llda_last_hi
            "llda_attr_sparse_struct_bytes", "llda_attribute_sparse",
            "llda_wcredit_sparse_struct_bytes", "llda_credit_words_sparse_scratch_bytes", "llda_credit_words_sparse",
            "llda_heldout_sparse_struct_bytes", "llda_heldout_loglik_sparse",
-           "llda_leftright_sparse_struct_bytes", "llda_left_to_right_sparse")
+           "llda_leftright_sparse_struct_bytes", "llda_left_to_right_sparse",
+           "llda_foldin_sparse_struct_bytes", "llda_foldin_sparse")
 
 _LIB = None
 
@@ -356,6 +365,10 @@ def lib():
     L.llda_leftright_sparse_struct_bytes.argtypes = []
     L.llda_left_to_right_sparse.restype = ctypes.c_int
     L.llda_left_to_right_sparse.argtypes = [ctypes.POINTER(LldaLeftrightSparseArgs), _c_p]
+    L.llda_foldin_sparse_struct_bytes.restype = ctypes.c_int
+    L.llda_foldin_sparse_struct_bytes.argtypes = []
+    L.llda_foldin_sparse.restype = ctypes.c_int
+    L.llda_foldin_sparse.argtypes = [ctypes.POINTER(LldaFoldinSparseArgs), _c_p]
     L.llda_selftest_div.restype = ctypes.c_int
     L.llda_selftest_div.argtypes = [_c_u64, _c_i64, _c_p, _c_p]
     if L.llda_abi_version() != ABI_VERSION:
@@ -381,7 +394,8 @@ def lib():
                                ("LldaAttrSparseArgs", LldaAttrSparseArgs, L.llda_attr_sparse_struct_bytes()),
                                ("LldaWcreditSparseArgs", LldaWcreditSparseArgs, L.llda_wcredit_sparse_struct_bytes()),
                                ("LldaHeldoutSparseArgs", LldaHeldoutSparseArgs, L.llda_heldout_sparse_struct_bytes()),
-                               ("LldaLeftrightSparseArgs", LldaLeftrightSparseArgs, L.llda_leftright_sparse_struct_bytes())):
+                               ("LldaLeftrightSparseArgs", LldaLeftrightSparseArgs, L.llda_leftright_sparse_struct_bytes()),
+                               ("LldaFoldinSparseArgs", LldaFoldinSparseArgs, L.llda_foldin_sparse_struct_bytes())):
         if size != ctypes.sizeof(struct):
             raise NativeError("%s: binding has %d bytes, the library %d" % (name, ctypes.sizeof(struct), size))
     _LIB = L
@@ -816,6 +830,19 @@ def left_to_right_sparse(doc_off, word, phi_t, lab_off, lab, D, V, K, NL, max_la
                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, int(max_labels), _ptr(mant), _ptr(expo),
                                 _ptr(tok), _ptr(bad), _ptr(status))
     _launch(phi_t, lib().llda_left_to_right_sparse, "llda_left_to_right_sparse", ctypes.byref(a))
+
+
+def foldin_sparse(doc_off, word, freq, phi_t, lab_off, lab, D, V, K, NL, max_labels, *, iters, thinning, alpha, c_init, c_loop, seed,
+                  stream_id, z, n_dk_s, th_s, ld_phi=None, doc_ids=None, doc_base=0, status=None):
+    """llda_foldin_sparse on the current torch stream: doc_off (int64 [D+1]) / word / freq (int32 [S]) the sites; phi_t (V, ld_phi)
+    float64 in reference topic order; the label sets lab_off (int64 [D+1]) / lab (int32 [NL]); doc_ids int64 [D] or None; z (int32
+    [S], the slot of every site), n_dk_s (int32 [NL]), th_s (float64 [NL]) the outputs; status int32 [1] or None."""
+    a = LldaFoldinSparseArgs(ctypes.sizeof(LldaFoldinSparseArgs), int(K), int(max_labels), int(iters), int(thinning),
+                             int(stream_id) & 0xFFFFFFFF, _ptr(doc_off), _ptr(word), _ptr(freq), _ptr(phi_t), _ptr(lab_off), _ptr(lab),
+                             _ptr(doc_ids), int(D), int(V), int(NL), int(phi_t.stride(0) if ld_phi is None else ld_phi), int(doc_base),
+                             float(alpha), float(c_init), float(c_loop), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(z), _ptr(n_dk_s),
+                             _ptr(th_s), _ptr(status))
+    _launch(phi_t, lib().llda_foldin_sparse, "llda_foldin_sparse", ctypes.byref(a))
 
 
 NEAREST_MAX_N = 16            # LLDA_NEAREST_MAX_N

@@ -61,6 +61,7 @@
 //   kernel_docsparse.hpp llda_attr_sparse_kernel, llda_wcredit_sparse_kernel   both on sparse label sets: a lane per label of the document, the word's sums in LDS
 //                       llda_heldout_sparse_kernel   the likelihood of held-out sites against the loads per slot
 //   kernel_lrsparse.hpp llda_leftright_sparse_kernel   left-to-right on a document's own labels: one particle per lane group, one count per lane
+//   kernel_foldinsparse.hpp llda_foldin_sparse_kernel   the test-time sampler on a document's own labels: 8 lanes per document, its list in registers
 //   this file           host side: layout (llda_layout_init), dispatch, C entry points
 #include <hip/hip_runtime.h>
 #include "build_info.hpp"
@@ -105,6 +106,7 @@
 #include "kernel_emfit.hpp"
 #include "kernel_docsparse.hpp"
 #include "kernel_lrsparse.hpp"
+#include "kernel_foldinsparse.hpp"
 
 namespace {
 
@@ -1646,6 +1648,40 @@ int llda_left_to_right_sparse(const llda_leftright_sparse_args *a, void *stream)
         if (rl) return rl;
         const int waves = (P.R * G.value + 63) / 64;                        // 64 / G particles per wavefront
         hipLaunchKernelGGL(kern, grid, dim3(64 * waves), lds, st, P);
+        return launched();
+    });
+}
+
+int llda_foldin_sparse_struct_bytes(void) { return (int)sizeof(llda_foldin_sparse_args); }
+
+int llda_foldin_sparse(const llda_foldin_sparse_args *a, void *stream)
+{
+    if (!a || a->struct_bytes != sizeof(llda_foldin_sparse_args)) return LLDA_E_BAD_ARG;
+    if (a->K < 1 || a->K > LLDA_MAX_K) return LLDA_E_BAD_K;
+    if (a->D < 0 || a->V < 1 || a->V > INT32_MAX || a->NL < 0 || a->ld_phi < a->K) return LLDA_E_BAD_ARG;
+    if (a->max_labels < 1 || a->max_labels > LLDA_SPARSE_MAX_LABELS || a->iters < 0 || a->thinning < 1) return LLDA_E_BAD_ARG;
+    if (!(a->c_init > 1.0) || !(a->c_loop > 1.0) || a->alpha != a->alpha) return LLDA_E_BAD_ARG;
+    if (a->D == 0) return LLDA_OK;
+    if (!a->doc_off || !a->word || !a->freq || !a->lab_off || !a->phi_t || !a->z || (a->NL > 0 && (!a->lab || !a->n_dk_s || !a->th_s)))
+        return LLDA_E_BAD_ARG;
+    if (a->V > INT64_MAX / a->ld_phi) return LLDA_E_BAD_ARG;
+    if (misaligned(7, a->doc_off, a->lab_off, a->phi_t, a->doc_ids, a->th_s) || misaligned(3, a->word, a->freq, a->lab, a->z, a->n_dk_s) ||
+        misaligned(3, a->status))
+        return LLDA_E_BAD_ARG;
+    static_assert(LLDA_SPARSE_MAX_LABELS == 32, "kernel_foldinsparse.hpp holds a list in 8 lanes of 4 slots");
+    FoldinSparseParams P;
+    memset(&P, 0, sizeof P);
+    P.doc_off = a->doc_off; P.word = a->word; P.freq = a->freq; P.phi_t = a->phi_t; P.doc_ids = a->doc_ids;
+    P.z = a->z; P.n_dk_s = a->n_dk_s; P.th_s = a->th_s; P.status = a->status;
+    P.sets.lab_off = a->lab_off; P.sets.lab = a->lab; P.sets.NL = a->NL; P.sets.max_labels = a->max_labels;
+    P.D = a->D; P.V = a->V; P.ld_phi = a->ld_phi; P.doc_base = a->doc_base;
+    P.alpha = a->alpha; P.c_init = a->c_init; P.c_loop = a->c_loop;
+    P.key0 = (uint32_t)a->seed; P.key1 = (uint32_t)(a->seed >> 32); P.stream_id = a->stream_id;
+    P.K = a->K; P.iters = a->iters; P.thinning = a->thinning;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_tiles = (P.D + FS_DOCS - 1) / FS_DOCS;
+    return visit_int<1, 2, 4>(foldin_sparse_slots(a->max_labels), [&](auto T) {
+        hipLaunchKernelGGL(llda_foldin_sparse_kernel<T.value>, doc_grid(n_tiles), dim3(FS_THREADS), 0, st, P, n_tiles);
         return launched();
     });
 }

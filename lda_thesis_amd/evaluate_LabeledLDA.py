@@ -55,6 +55,10 @@ def build_parser():
     p.add_option("--lr-sparse", action="store_true", dest="lr_sparse", default=False,
                  help="with --left-to-right: score every test document against its own labels (the ones the model knows, and "
                       "'root') through the sparse-label kernel (llda_left_to_right_sparse): p(w_d | labels_d), for every K")
+    p.add_option("--shortlist", dest="shortlist", type="int", default=0, metavar="M",
+                 help="after the report: the same four metrics with the fold-in sampler run on a shortlist of every test document: "
+                      "'root' plus the M <= 16 labels with the most credit after one attribution pass (llda_attribute, "
+                      "llda_rank_labels, llda_foldin_sparse); a site then costs M + 1 loadings per sweep, not K")
     p.add_option("--heldout-em", dest="heldout_em", type="int", default=0, metavar="ITERS",
                  help="after the report: perplexity of the held-out documents by document completion without random numbers: the "
                       "observed half folded in by ITERS EM steps (llda_attribute, llda_heldout_loglik); with --em-sparse against "
@@ -153,6 +157,19 @@ def report_em_foldin(model, test, iters):
     print("two error:               ", m["two_error"])
     print("F1 score (macro average) ", m["f1"])
     return m
+
+
+def report_shortlist(model, test, it, thinning, m):
+    """the four metrics of the report for the sampler on root plus the m best-credited labels (LabeledLDA.score_test(shortlist=m))"""
+    known = set(model.vocab)
+    r = model.score_test([[x for x in doc if x in known] for doc in test[0]], test[1], it, thinning, shortlist=m)
+    print("-----------------------------------")
+    print("Fold-in on a shortlist of %d labels per document:" % m)
+    print("AUC ROC:                 ", r["auc"])
+    print("one error:               ", r["one_error"])
+    print("two error:               ", r["two_error"])
+    print("F1 score (macro average) ", r["f1"])
+    return r
 
 
 def report_explain(model, test, n_docs, iters):
@@ -346,6 +363,8 @@ def main(argv=None):
         report_heldout(model, test, opt.it, opt.thinning)
     if opt.left_to_right:
         report_left_to_right(model, test, opt.left_to_right, sparse=opt.lr_sparse)
+    if opt.shortlist:
+        report_shortlist(model, test, opt.it, opt.thinning, opt.shortlist)
     if opt.heldout_em:
         report_heldout_em(model, test, opt.heldout_em, sparse=opt.em_sparse)
     if opt.em_foldin:

@@ -165,6 +165,51 @@ def fold_in(ph_hat, alpha, doc_tups, it, thinning, seed, stream_id=TEST_STREAM, 
     return pending.th_device() if keep_device else pending.result()
 
 
+def fold_in_sparse(phi_t, alpha, doc_tups, lab_off, lab, it, thinning, seed, stream_id=TEST_STREAM, doc_base=0, keep_device=False):
+    """``fold_in`` with every document's topics restricted to its own label list (``llda_foldin_sparse``).  phi_t: the
+    (V, K) float64 tensor on the device in reference topic order (the document model's matrix, ``ph_hat.T``); the lists are the CSR
+    lab_off (int64 [D+1]) / lab (``docmodel.label_csr``: ids ascending, at most 32 per document).  A site touches len(labels) entries
+    of its word's row, whatever K is.  The result is that of ``fold_in`` on the document's own rows of ph_hat: the same constants,
+    the same RNG ids doc_base + d, the same ValueError where a site has no positive probability.
+    Returns dict(th_s float64 [NL], n_dk_s int64 [NL], z: one int array of SLOTS per document) -- per slot of the lists, nothing of
+    size (D, K); keep_device=True: (th_s, lab_off, lab) as tensors on the device.  ValueError on the host, before any launch, for
+    label sets the kernel would call unfit."""
+    from . import docmodel
+    if not (isinstance(phi_t, torch.Tensor) and phi_t.dim() == 2):
+        raise ValueError("phi_t must be a two-dimensional float64 tensor on the device")
+    D = len(doc_tups)
+    loff_h, lab_h, NL, max_labels = docmodel.label_sets(lab_off, lab, D, int(phi_t.shape[1]))      # (before any launch)
+    for doc in doc_tups:
+        if not doc:
+            raise ValueError("not enough values to unpack: a document has no in-vocabulary word")
+    if int(it) < 0 or int(thinning) < 1:
+        raise ValueError("it must be >= 0 and thinning >= 1")
+    _native.lib()
+    _native.require_device()
+    x = docmodel.matrix(phi_t, "phi_t")
+    dev = x.device
+    V, K = int(x.shape[0]), int(x.shape[1])
+    doc_off, word, freq = csr_from_doc_tups(doc_tups)
+    S = int(doc_off[-1])
+    d_off, d_word, d_freq = docmodel.stage(dev, doc_off, word, freq, S, V=V)
+    d_loff = docmodel.on_dev(loff_h, torch.int64, dev)
+    d_lab = docmodel.on_dev(lab_h if NL else np.zeros(1), torch.int32, dev)
+    z = torch.zeros((max(S, 1),), dtype=torch.int32, device=dev)
+    n_dk_s = torch.zeros((max(NL, 1),), dtype=torch.int32, device=dev)
+    th_s = torch.zeros((max(NL, 1),), dtype=torch.float64, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _native.foldin_sparse(d_off, d_word, d_freq, x, d_loff, d_lab, D, V, K, NL, max_labels, iters=int(it), thinning=int(thinning),
+                          alpha=float(alpha), c_init=1.0000000005, c_loop=1.0000005, seed=seed, stream_id=stream_id, z=z, n_dk_s=n_dk_s,
+                          th_s=th_s, ld_phi=int(x.stride(0)) if V > 1 else K, doc_base=int(doc_base), status=status)
+    if int(status.item()) & 1:                                  # (synchronises with the launch)
+        raise ValueError("pvals < 0, pvals > 1 or pvals contains NaNs")     # numpy.random.multinomial's complaint
+    if keep_device:
+        return th_s[:NL], d_loff, d_lab[:NL]
+    zh = z.cpu().numpy()
+    return dict(th_s=th_s[:NL].cpu().numpy(), n_dk_s=n_dk_s[:NL].cpu().numpy().astype(np.int64),
+                z=[zh[doc_off[d]:doc_off[d + 1]] for d in range(D)])
+
+
 # ------------------------------------------------------------------------------------------------
 # CascadeLDA
 # ------------------------------------------------------------------------------------------------
